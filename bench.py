@@ -119,7 +119,35 @@ def parse_args(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="skip the extra measurements after the timed region (batch 1, N = 60, max_iter 150, tuned warm start)")
     ap.add_argument("--selftest-stub", action="store_true", help="CPU-only plumbing test of the multi-rank path (tests/test_distributed_cpu.py): gloo "
                     "instead of RCCL and a stand-in for the solver; the line it prints says data = stub and is not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed ticks, write what the last of them returned for every "
+                    "instance of the batch (all ranks) as DIR/<name>.npy in float64: u0 (controls), x_next (states after the plant step), status, "
+                    "iters; at most 64 MB in all (beyond that the same seeded sample of rows of each, listed in DIR/sample_rows.npy)")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def write_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> (rows, ...), the same rows in each) as out_dir/<name>.npy in float64.
+    When they would take more than max_bytes together, a fixed, seeded sample of rows (sorted; the same rows of every array)
+    is written instead, and its row indices as sample_rows.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    stale = os.path.join(out_dir, "sample_rows.npy")
+    if n * row_bytes > max_bytes:
+        keep = max_bytes // (row_bytes + 8) - 16  # (+ 8: the index of a row; 16 rows: room for the .npy headers)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    elif os.path.exists(stale):
+        os.remove(stale)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    print(f"bench.py: wrote {', '.join(f'{k}{v.shape}' for k, v in arrays.items())} to {out_dir}", file=sys.stderr)
 
 
 def launch_ranks(args) -> int:
@@ -159,7 +187,8 @@ def stub_main(args):
     if world > 1:
         dist.init_process_group("gloo", rank=rank, world_size=world)
     def shape(total):
-        """one timed region: total = 0 -> args.batch per rank (weak), else `total` instances sharded over the ranks (strong)"""
+        """one timed region: total = 0 -> args.batch per rank (weak), else `total` instances sharded over the ranks (strong);
+        returns its figures and the rows its last step gathered"""
         lo, hi = shard.shard_range(total, rank, world) if total else (rank * args.batch, (rank + 1) * args.batch)
         Bl, n_all = hi - lo, (total if total else args.batch * world)
         for _ in range(args.warmup):
@@ -176,6 +205,7 @@ def stub_main(args):
             assert g.shape == (n_all, 2) and float(g[-1, 0]) == n_all - 1 + k
             checksum += float(g.sum())
         elapsed = time.perf_counter() - t0
+        last = g  # what the last step gathered (--dump-outputs)
         if world > 1:
             dist.barrier()
         _, _, elapsed_max = shard.reduce_stats(0, 0, elapsed)
@@ -183,9 +213,11 @@ def stub_main(args):
         if world > 1:
             dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         return dict(value=float(tot.item()) / elapsed_max, ms_per_step=1e3 * elapsed_max / args.steps, converged_solves=float(tot.item()),
-                    batch_per_gpu=Bl, total_batch=n_all, gathered_checksum=checksum)
-    head = shape(args.total_batch)
-    extra = shape(8192) if (world > 1 and not args.total_batch) else None
+                    batch_per_gpu=Bl, total_batch=n_all, gathered_checksum=checksum), last
+    head, last = shape(args.total_batch)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, {"u0": last.numpy()})
+    extra = shape(8192)[0] if (world > 1 and not args.total_batch) else None
     if rank == 0:
         out = {"metric": "MPC solves/sec (N=40, nx=8 [7 + progress s], nu=2)", "value": head["value"], "unit": "MPC solves/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
@@ -392,6 +424,16 @@ def main():
     tm = prof.timing()
     log = prof.launch_log(with_iterations=True) if not args.no_profile else None
     mpc.set_profiling(False)
+
+    if args.dump_outputs:
+        # what the last timed tick returned for every instance: its controls (split handles on several ranks: the ring slot of
+        # that tick), the states its plant step produced, and each solve's status and iteration count (make_step's outputs)
+        u_last = u_ring[(args.steps - 1) % len(u_ring)] if (split and world > 1) else u
+        st = mpc.stats()
+        rows = torch.cat([u_last, x, torch.from_numpy(np.stack([st["status"], st["iters"]], 1).astype(np.float64)).to(dev)], 1)
+        rows = shard.gather_rows(rows, n_total, rank, world).cpu().numpy()
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"u0": rows[:, :2], "x_next": rows[:, 2:10], "status": rows[:, 10], "iters": rows[:, 11]})
 
     counts = np.array(per_tick_counts, dtype=np.float64)  # (K, 8)
     scounts = np.array(per_tick_solver, dtype=np.float64)  # (K, 8): the solver's own statuses (before the node-0 rule)
