@@ -209,7 +209,9 @@ const char* ltompc_version(void);
 /* Replaces Controller(model, control_costs, n_horizon, t_step) + mpc.setup()   (controller.py:9-34).
  * tables: LTOMPC_TABLE_ROWS x n_table doubles, row-major (rows as named above; path.py:96-101,
  *         mpc/track.py:30-42).  n_horizon = N; batch = number of independent MPC instances;
- * device: HIP device ordinal.  Allocates every device workspace; no allocation happens per call later. */
+ * device: HIP device ordinal.  Allocates every device workspace; no allocation happens per call later, except the workspaces
+ * of the sensitivity pass (ltompc_get_sensitivities / ltompc_sensitivities_dev), allocated on the handle's first request for
+ * sensitivities: a handle that never asks for them pays nothing. */
 int ltompc_create(const ltompc_params* params, const ltompc_options* options, const double* tables,
                   int n_table, int n_horizon, int batch, int device, ltompc_handle* out);
 int ltompc_destroy(ltompc_handle h);
@@ -297,6 +299,41 @@ int ltompc_get_restoration(ltompc_handle h, int* n_resto, double* violation);
  * solver_status - the solver's own termination status, before the node-0 rule; penalty - the elastic variables' penalty at
  * termination (0: hard constraints; resto_rho_max for status INFEASIBLE after an escalated restoration). */
 int ltompc_get_recovery(ltompc_handle h, int* n_shift, int* n_fallback, double* g0, int* solver_status, double* penalty);
+
+/* Parametric sensitivities of the last solve's solution w.r.t. p = (x0[0..7], u_prev[0..1]): 10 columns, in that order.
+ * u_prev is the previous input of the Delta-u cost that solve used (0 after set_initial_guess, the u0 of the solve before otherwise).
+ *
+ * Definition.  For an instance whose last solve ended with the solver's own status SOLVED or ACCEPTABLE (solver_status of
+ * ltompc_get_recovery, i.e. before the node-0 rule) these are the derivatives of the solution of the BARRIER problem at the
+ * final iterate - the final barrier parameter and the final table smoothing - obtained from the KKT matrix at that iterate
+ * with delta_w = 0 (implicit-function theorem, as in sIPOPT).  du0/dx0 = K_0 and du0/du_prev = Kv_0, the
+ * stage-0 gains of the Riccati factorisation of that matrix.  An instance that the node-0 rule reports as INFEASIBLE is covered
+ * the same way: its u0 is the control of the NLP without the constant node-0 rows, and these are that NLP's sensitivities.
+ *   ok[b] = 1 when the status condition holds, the factorisation at delta_w = 0 passes the inertia test (every stage's Huu
+ *   positive definite: the reduced Hessian is positive definite) and every output is finite.  Otherwise ok[b] = 0 and every
+ *   output of the instance (margin included) is exactly 0 - not NaN: a caller that applies the feedback blindly gets u0.
+ *   margin[b] = min over the (slack, multiplier) pairs of the inequalities of max(t, nu), unscaled.  In an interior-point
+ *   solution t nu ~ mu; a small margin (<< 1) marks a weakly active constraint, where the true derivative is one-sided and
+ *   the barrier derivative a smoothed value.
+ *
+ * ltompc_get_sensitivities: host outputs in the caller's instance order, any may be NULL:
+ *   du0_dp  batch x 2 x 10;
+ *   dX_dp   batch x (N+1) x 8 x 10, row block 0 is [I_8 | 0] (by definition);
+ *   dU_dp   batch x N x 2 x 10, block 0 equals du0_dp;
+ *   ok      batch ints;  margin  batch doubles.
+ * ltompc_sensitivities_dev: enqueues only, on the handle's stream: du0_dp_dev (row-major batch x 2 x 10) and ok_dev (batch
+ *   ints), device pointers, either may be NULL.  This is the feedback use (u = u0 + du0_dp (p - p_solved)): no host round trip.
+ *   Exception: the FIRST request for sensitivities on a handle (either function) allocates the pass's workspaces and
+ *   synchronises the handle's stream once; call one of them once after the first solve (e.g. with NULL outputs) to keep
+ *   every later call asynchronous.
+ *
+ * The result refers to the last solve of each instance (make_step, make_step_dev or rollout_dev).  It is computed on the
+ * first request after that solve (re-linearisation at the final iterate, a head-less Riccati sweep, the forward propagation
+ * of the 10 directions; the trajectories only when dX_dp or dU_dp is asked for) and cached until the next solve,
+ * set_initial_guess or set_initial_guess_dev.  Before any solve, and after set_initial_guess, a call is a usage error.  The
+ * pass writes buffers of its own only: every later make_step or rollout gives the bits it would have given without it. */
+int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, double* dU_dp, int* ok, double* margin);
+int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev);
 
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:

@@ -20,6 +20,8 @@
 //                 front of the batch, k_compact re-packs the index list only), I/O, k_plant (RK4 plant step), test hooks
 //   rollout.h     k_roll_*: closed-loop rollout with free-running instances (ltompc_rollout_dev)
 //   velocity.h    k_velocity_profile: the forward / backward speed-profile passes of src/velocity.py
+//   sensitivity.h k_sens_*: parametric sensitivities of the solution w.r.t. (x0, u_prev) at the final iterate
+//                 (ltompc_get_sensitivities): re-linearisation, head-less Riccati sweep at delta_w = 0, forward propagation
 #pragma once
 #include "layout.h"
 #include "linearise.h"
@@ -29,3 +31,4 @@
 #include "eval8.h"
 #include "velocity.h"
 #include "rollout.h"
+#include "sensitivity.h"

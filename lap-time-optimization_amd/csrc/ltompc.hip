@@ -92,6 +92,14 @@ struct ltompc_solver {
                          // beside other handles' kernels its 4-wavefront workgroups gain nothing at 64 and lose 1 % at 512, alone it is 7 % faster)
   int ric1_width = 512;  // LTOMPC_RIC1: launches of at most this many instances use the one-wavefront-per-instance sweep (0 = never)
   int last_launches = 0, last_iterations = 0;
+  // parametric sensitivities (sensitivity.h, ltompc_get_sensitivities): the pass's own buffers, allocated on the first request.
+  // sens_state: 0 no solve to differentiate, 1 a solve to differentiate, 2 du0 / ok / margin computed, 3 trajectories too
+  int sens_state = 0;
+  bool sens_moved = false;  // the instances were moved (un-packed) after the pass: its stage / Riccati blocks are not where they were
+  Work Ws{};                // W with QP, RC, RS, LS -> the pass's buffers, si -> zeros
+  Work* d_Ws = nullptr;
+  int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
+  double *d_sens_du0 = nullptr, *d_sens_margin = nullptr, *d_sens_dX = nullptr, *d_sens_dU = nullptr;
 
   // (P may be a gptr<T>: a global-address-space pointer in the device pass of the compiler, a plain one on the host)
   // work = true: an array that the kernels fill before they read it.  LTOMPC_POISON=1 (debug) fills those with 0xFF bytes
@@ -243,6 +251,57 @@ int ensure_unpacked(ltompc_solver* h) {
                        h->K.bd.ni, h->K.bd.nel, pass);
   HIPCHECK(hipGetLastError());
   h->packed = false;
+  if (h->sens_state >= 2) h->sens_moved = true;
+  return 0;
+}
+
+// The sensitivity pass of the last solve (sensitivity.h), enqueued on the handle's stream: linearisation and head-less sweep
+// when not done since that solve (or when the instances have moved since), the forward pass for du0 / ok / margin, and the
+// trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
+int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
+  if (h->sens_state == 0) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess discards the last solve)");
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!h->d_Ws) {
+    Work& Ws = h->Ws;
+    Ws = h->W;
+    int rc = 0;
+    rc |= h->dalloc(&Ws.QP, (size_t)QP_NF * (N + 1) * Bp, true), rc |= h->dalloc(&Ws.RC, (size_t)RC_NF * (N + 1) * Bp, true);
+    rc |= h->dalloc(&Ws.RS, (size_t)RS_NF * N * Bp, true), rc |= h->dalloc(&Ws.LS, (size_t)3 * N * Bp, true);
+    rc |= h->dalloc(&Ws.si, (size_t)SI_NF * Bp);  // zeros, never written
+    rc |= h->dalloc(&h->d_sens_inertia, Bp), rc |= h->dalloc(&h->d_sens_ok, Bp);
+    rc |= h->dalloc(&h->d_sens_du0, (size_t)2 * SENS_NP * B), rc |= h->dalloc(&h->d_sens_margin, B);
+    rc |= h->dalloc(&h->d_Ws, 1);
+    if (rc) return -1;
+    HIPCHECK(hipMemcpyAsync(h->d_Ws, &h->Ws, sizeof(Work), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  }
+  auto factorise = [&]() {
+    const bool ell = h->K.bd.nel > 0;  // the evaluation kernels the solve used (launch_iteration)
+    if (h->eval8) hipLaunchKernelGGL(k_sens_eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
+    else
+      hipLaunchKernelGGL(ell ? (h->ref_eval ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
+                             : (h->ref_eval ? k_sens_eval<BoundsRef, false> : k_sens_eval<BoundsAny, false>),
+                         dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
+    hipLaunchKernelGGL(k_sens_riccati8, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, h->Ws, (const int*)h->W.si, h->d_sens_inertia);
+  };
+  if (h->sens_state == 1) {
+    factorise();
+    hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, (const int*)h->d_sens_inertia, h->K.bd.ni, h->d_sens_du0,
+                       h->d_sens_ok, h->d_sens_margin, (double*)nullptr, (double*)nullptr, (const int*)nullptr);
+    h->sens_state = 2, h->sens_moved = false;
+  }
+  if (traj && h->sens_state == 2) {
+    if (!h->d_sens_dX) {
+      int rc = h->dalloc(&h->d_sens_dX, (size_t)(N + 1) * 8 * SENS_NP * B);
+      rc |= h->dalloc(&h->d_sens_dU, (size_t)N * 2 * SENS_NP * B);
+      if (rc) return -1;
+    }
+    if (h->sens_moved) factorise();  // (same blocks, same bits, at the instances' new slots)
+    hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, (const int*)h->d_sens_inertia, h->K.bd.ni, (double*)nullptr,
+                       (int*)nullptr, (double*)nullptr, h->d_sens_dX, h->d_sens_dU, (const int*)h->d_sens_ok);
+    h->sens_state = 3, h->sens_moved = false;
+  }
+  HIPCHECK(hipGetLastError());
   return 0;
 }
 
@@ -489,6 +548,7 @@ int ltompc_set_initial_guess_dev(ltompc_handle h, const double* x0_dev) {
   if (!h || !x0_dev) return fail("ltompc_set_initial_guess: null argument");
   HIPCHECK(hipSetDevice(h->device));
   h->packed = false;  // a cold start overwrites the whole iterate: nothing to restore
+  h->sens_state = 0;  // (nor a solve to differentiate)
   hipLaunchKernelGGL(k_act_identity, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->d_orig, h->d_perm, h->B);  // (slot -> caller's index: identity again)
   hipLaunchKernelGGL(k_load_x0, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)nullptr, 0, 0);
   hipLaunchKernelGGL(k_zero_uprev, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -514,6 +574,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   const int B = h->B, N = h->N, Bp = h->Bp;
   const bool ell = h->K.bd.nel > 0;  // kernels instantiated with / without the friction-ellipse constraints
   Launcher L{h};
+  h->sens_state = 0;
   hipLaunchKernelGGL(k_load_x0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)(h->packed ? h->d_orig : nullptr),
                      h->K.o.resto_sticky, h->cold_next ? 0 : 1);
   if (h->cold_next) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -595,6 +656,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   HIPCHECK(hipGetLastError());
   h->last_launches = L.launches + 3;
   h->last_iterations = it + 1;
+  h->sens_state = 1;
   if (h->profiling) {
     HIPCHECK(hipStreamSynchronize(h->stream));
     if (collect_profile(h)) return -1;
@@ -689,6 +751,7 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   if (h->eval8) return fail("ltompc_rollout: latency-mode handles (8-lanes-per-slot kernels) are not supported by the rollout");
   HIPCHECK(hipSetDevice(h->device));
   if (ensure_unpacked(h)) return -1;  // the rollout works in the caller's order (index-list compaction only)
+  h->sens_state = 0;
   constexpr int RING = ltompc_solver::ROLL_RING;
   if (!h->plant_streams[0]) {
     // low priority: the plant steps are not urgent, and the runtime keeps a pool of hardware queues per priority level, so
@@ -795,7 +858,32 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   h->roll_iterations = it + 1, h->roll_launches = L.launches;
   h->last_iterations = 0;  // (no per-iteration history after a rollout: ltompc_get_active_history returns 0)
   h->after_rollout = true;
+  if (rc == 0) h->sens_state = 1;
   return rc;
+}
+
+int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, double* dU_dp, int* ok, double* margin) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (sens_compute(h, dX_dp || dU_dp, "ltompc_get_sensitivities")) return -1;
+  const size_t B = h->B, N = h->N;
+  if (du0_dp) HIPCHECK(hipMemcpyAsync(du0_dp, h->d_sens_du0, sizeof(double) * 2 * SENS_NP * B, hipMemcpyDeviceToHost, h->stream));
+  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+  if (margin) HIPCHECK(hipMemcpyAsync(margin, h->d_sens_margin, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
+  if (dX_dp) HIPCHECK(hipMemcpyAsync(dX_dp, h->d_sens_dX, sizeof(double) * (N + 1) * 8 * SENS_NP * B, hipMemcpyDeviceToHost, h->stream));
+  if (dU_dp) HIPCHECK(hipMemcpyAsync(dU_dp, h->d_sens_dU, sizeof(double) * N * 2 * SENS_NP * B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (sens_compute(h, false, "ltompc_sensitivities_dev")) return -1;
+  const size_t B = h->B;
+  if (du0_dp_dev) HIPCHECK(hipMemcpyAsync(du0_dp_dev, h->d_sens_du0, sizeof(double) * 2 * SENS_NP * B, hipMemcpyDeviceToDevice, h->stream));
+  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
 }
 
 int ltompc_rollout_info(ltompc_handle h, long long* iterations, long long* launches) {

@@ -556,22 +556,35 @@ struct FwdRegs {
 
 // All 64 lanes of a wavefront call this together; lane (g, i) works on row i of instance b (padding lanes: valid =
 // false, they shadow a real instance read-only).  active_slot >= 0: count the unfinished instances there.
+// SENS (sensitivity.h): the head-less factorisation at the final iterate - no head, delta_w = 0, one sweep, no schedule,
+// no status writes, no rollout; sens_live selects the instances whose gains are stored, sens_inertia[b] gets 1 when every
+// stage's Huu passed the inertia test.  The solver's instantiation (SENS = false) is unchanged.
+template <bool SENS = false>
 __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLds& L, const int g, const int i, const int b,
-                                           const bool valid, const int active_slot, const int max_sweeps) {
+                                           const bool valid, const int active_slot, const int max_sweeps, const bool sens_live = false,
+                                           int* sens_inertia = nullptr) {
   const int N = W.N;
   double* st = W.st;
   int* si = W.si;
   const ltompc_options& o = K.o;
   bool live, retry;
   double mu;
-  if (!d_head8(K, W, i, b, valid, active_slot, live, retry, mu)) return;
+  if constexpr (SENS) {
+    live = sens_live, retry = false, mu = STD(ST_MU);
+    if (!__any(live)) {
+      if (valid && i == 0) sens_inertia[b] = 0;
+      return;
+    }
+  } else {
+    if (!d_head8(K, W, i, b, valid, active_slot, live, retry, mu)) return;
+  }
   // ---- backward sweep (whole wave in lock-step; an instance whose Huu fails retries with a larger delta_w,
   //      the others recompute the same numbers)
   const double r2[2] = {2.0 * K.p.r_du[0], 2.0 * K.p.r_du[1]};
   const double psc = pen_scale(STD(ST_RHO));  // penalty scale (layout.h): the regularisation schedule in its units
-  double delta_w = STD(ST_FORCE_REG);
+  double delta_w = SENS ? 0.0 : STD(ST_FORCE_REG);
   const double dw_last = STD(ST_DW_LAST);
-  if (delta_w == 0.0 && dw_last > DW_KEEP * psc) delta_w = dw_last / 3.0;  // see DESIGN.md §3 (deviation from Algorithm IC)
+  if (!SENS && delta_w == 0.0 && dw_last > DW_KEEP * psc) delta_w = dw_last / 3.0;  // see DESIGN.md §3 (deviation from Algorithm IC)
   int tries = 0;
   if (retry) delta_w = STD(ST_DW_TRY), tries = STI(SI_TRIES);
   bool numerical = false;
@@ -790,6 +803,10 @@ __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLd
           PG(W.RC, RC_pp + i, k, RC_NF) = ppi;
         }
       }
+    }
+    if constexpr (SENS) {
+      if (valid && i == 0) sens_inertia[b] = (live && ok) ? 1 : 0;
+      return;
     }
     // inertia correction schedule per instance (Waechter & Biegler 2006, Algorithm IC)
     const bool failed = live && !ok;

@@ -109,6 +109,11 @@ class _MPC:
         self.solver_stats = dict(status=self._solver.status.copy(), iters=self._solver.iters.copy())
         return u0.reshape(2, 1) if single else u0
 
+    def sensitivities(self, trajectory: bool = False):
+        """Parametric sensitivities of the last make_step's solution w.r.t. (x0, u_prev) (BatchedMPC.sensitivities; do_mpc
+        ships a differentiator for the same quantities)."""
+        return self._solver.sensitivities(trajectory)
+
 
 class Controller:
     """src/mpc/controller.py:9-34: NLP weights, bounds and IPOPT settings; builds the device solver."""

@@ -28,6 +28,11 @@ class BatchedMPC:
         self._h = C.c_void_p()
         check(lib().ltompc_create(C.byref(self.params), C.byref(self.options), dptr(self._tab), self._tab.shape[1],
                                   self.N, self.B, int(device), C.byref(self._h)))
+        # the parameters p = (x0, u_prev) of the last solve and its u0 (feedback()); the next solve's u_prev is this u0, or 0
+        # after an initial guess.  None where the host does not see them (make_step_dev, rollout_dev).
+        self._solved = None
+        self._fb = None  # (du0_dx0, du0_duprev, ok) of that solve, fetched by the first feedback()
+        self._uprev_next = np.zeros((self.B, NU))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -44,13 +49,20 @@ class BatchedMPC:
     def set_initial_guess(self, x0):
         x0 = self._x(x0)
         check(lib().ltompc_set_initial_guess(self._h, dptr(x0)))
+        self._solved, self._uprev_next = None, np.zeros((self.B, NU))
+        self._fb = None
 
     def make_step(self, x0):
         x0 = self._x(x0)
         u0 = np.empty((self.B, NU))
         self.status = np.empty(self.B, dtype=np.int32)
         self.iters = np.empty(self.B, dtype=np.int32)
+        self._solved = None
+        self._fb = None
         check(lib().ltompc_make_step(self._h, dptr(x0), dptr(u0), iptr(self.status), iptr(self.iters)))
+        if self._uprev_next is not None:
+            self._solved = (x0.copy(), self._uprev_next.copy(), u0.copy())
+        self._uprev_next = u0.copy()
         return u0
 
     # ---- device-pointer variants (bench, closed loop on the GPU) --------------------------------
@@ -59,12 +71,18 @@ class BatchedMPC:
 
     def set_initial_guess_dev(self, x0_ptr: int):
         check(lib().ltompc_set_initial_guess_dev(self._h, C.c_void_p(x0_ptr)))
+        self._solved, self._uprev_next = None, np.zeros((self.B, NU))
+        self._fb = None
 
     def make_step_dev(self, x0_ptr: int, u0_ptr: int):
+        self._solved = self._uprev_next = None
+        self._fb = None
         check(lib().ltompc_make_step_dev(self._h, C.c_void_p(x0_ptr), C.c_void_p(u0_ptr)))
 
     def rollout_dev(self, x_ptr: int, n_ticks: int, n_sub: int = 400, u_log_ptr: int = 0, status_log_ptr: int = 0, iters_log_ptr: int = 0):
         """Closed-loop rollout with free-running instances (ltompc_rollout_dev): n_ticks of make_step + plant step per instance."""
+        self._solved = self._uprev_next = None
+        self._fb = None
         check(lib().ltompc_rollout_dev(self._h, C.c_void_p(x_ptr), int(n_ticks), int(n_sub), C.c_void_p(u_log_ptr or None),
                                        C.c_void_p(status_log_ptr or None), C.c_void_p(iters_log_ptr or None)))
         it, ln = C.c_longlong(), C.c_longlong()
@@ -73,6 +91,47 @@ class BatchedMPC:
 
     def plant_step_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int, n_sub: int = 400):
         check(lib().ltompc_plant_step_dev(self._h, C.c_void_p(x_ptr), C.c_void_p(u_ptr), int(n_sub), C.c_void_p(xn_ptr)))
+
+    # ---- parametric sensitivities (ltompc_get_sensitivities) -----------------------
+    def sensitivities(self, trajectory: bool = False):
+        """Derivatives of the last solve's solution w.r.t. p = (x0, u_prev), at its final iterate (include/ltompc.h).
+
+        Returns du0_dx0 (B,2,8), du0_duprev (B,2,2), ok (B,) bool, margin (B,) and, with trajectory=True, dX (B,N+1,8,10) and
+        dU (B,N,2,10) (columns: x0[0..7], u_prev[0..1]).  Where ok is False every output of the instance is 0."""
+        B, N = self.B, self.N
+        du0, ok, margin = np.empty((B, NU, 10)), np.empty(B, dtype=np.int32), np.empty(B)
+        dX = np.empty((B, N + 1, NX, 10)) if trajectory else None
+        dU = np.empty((B, N, NU, 10)) if trajectory else None
+        check(lib().ltompc_get_sensitivities(self._h, dptr(du0), dptr(dX) if trajectory else None, dptr(dU) if trajectory else None,
+                                             iptr(ok), dptr(margin)))
+        out = dict(du0_dx0=du0[:, :, :NX].copy(), du0_duprev=du0[:, :, NX:].copy(), ok=ok != 0, margin=margin)
+        if trajectory:
+            out.update(dX=dX, dU=dU)
+        return out
+
+    def sensitivities_dev(self, du0_dp_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue the sensitivities of the last solve into device buffers (B,2,10) doubles / (B,) int32, on the handle's stream."""
+        check(lib().ltompc_sensitivities_dev(self._h, C.c_void_p(du0_dp_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    def solved_parameters(self):
+        """(x0, u_prev, u0) of the last make_step, (B,8), (B,2), (B,2); None after make_step_dev / rollout_dev / set_initial_guess."""
+        return self._solved
+
+    def feedback(self, x, u_prev=None):
+        """Tangential predictor of the last make_step: u0 + du0_dx0 (x - x0_solved) + du0_duprev (u_prev - u_prev_solved), and u0
+        where ok is False.  u_prev=None: the u_prev of that solve (no change in those directions)."""
+        if self._solved is None:
+            raise _lib.LtompcError("feedback: no make_step to expand around (the last solve was not a host make_step, or an "
+                                   "initial guess came after it)")
+        x0s, ups, u0 = self._solved
+        x = self._x(x)
+        up = ups if u_prev is None else np.asarray(u_prev, dtype=np.float64).reshape(self.B, NU)
+        if self._fb is None:  # one host copy per solve, not per call
+            S = self.sensitivities()
+            self._fb = (S["du0_dx0"], S["du0_duprev"], S["ok"])
+        Jx, Ju, ok = self._fb
+        u = u0 + np.einsum("bij,bj->bi", Jx, x - x0s) + np.einsum("bij,bj->bi", Ju, up - ups)
+        return np.where(ok[:, None], u, u0)
 
     # ---- results --------------------------------------------------------------------------------
     def prediction(self):
@@ -315,3 +374,13 @@ class SplitMPC:
     def iterate(self):
         r = [p.iterate() for p in self.parts]
         return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    def sensitivities(self, trajectory: bool = False):
+        """BatchedMPC.sensitivities of every part, stitched in the caller's order."""
+        r = [p.sensitivities(trajectory) for p in self.parts]
+        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    def sensitivities_dev(self, du0_dp_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.sensitivities_dev of every part into its rows of (B,2,10) doubles / (B,) int32, each on its part's stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.sensitivities_dev(du0_dp_ptr + 8 * NU * 10 * lo if du0_dp_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
