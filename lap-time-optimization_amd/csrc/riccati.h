@@ -739,9 +739,13 @@ __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLd
 #undef LB
 #undef Lb
       double det = Huu[0] * Huu[3] - Huu[1] * Huu[2];
-      bool bad = !(Huu[0] > 0.0) || !(det > 1e-14 * Huu[0] * Huu[3]) || !isfinite(det);
+      // (the test and its fix-up are branch-free selects: written as short-circuit branches, they made the compiler keep
+      //  Huu in scratch memory across the LDS reads above, and each reload waited for the stage block in flight; with
+      //  them the kernel spilled 102 VGPRs and shuttled ~240 values per stage through AGPRs, now none)
+      const bool bad = !(Huu[0] > 0.0) | !(det > 1e-14 * Huu[0] * Huu[3]) | !isfinite(det);
       if (bad && live) ok = false;
-      if (bad) det = 1.0, Huu[0] = Huu[3] = 1.0, Huu[1] = Huu[2] = 0.0;  // keep the lock-step arithmetic finite
+      det = bad ? 1.0 : det;  // keep the lock-step arithmetic finite
+      Huu[0] = bad ? 1.0 : Huu[0], Huu[3] = bad ? 1.0 : Huu[3], Huu[1] = bad ? 0.0 : Huu[1], Huu[2] = bad ? 0.0 : Huu[2];
       const double idet = 1.0 / det;  // one division per stage instead of four (same expression in the three Riccati kernels)
       double Hi[4] = {Huu[3] * idet, -Huu[1] * idet, -Huu[2] * idet, Huu[0] * idet};
       double Kc[2], Kv[4], kff[2];
