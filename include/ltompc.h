@@ -30,6 +30,7 @@ extern "C" {
 #define LTOMPC_NU 2
 #define LTOMPC_NO_BOUND 1.0e30 /* |bound| >= this means "not set" (controller.py:78 `not_set`) */
 #define LTOMPC_TABLE_ROWS 6    /* s_kappa, kappa, s_arc, n_left, n_right, v_ref */
+#define LTOMPC_NTHETA 16       /* columns of ltompc_get_param_sensitivities (order given there)   */
 
 /* per-instance solver status written by make_step */
 #define LTOMPC_STATUS_SOLVED 0          /* scaled KKT error <= tol                                */
@@ -334,6 +335,35 @@ int ltompc_get_recovery(ltompc_handle h, int* n_shift, int* n_fallback, double* 
  * pass writes buffers of its own only: every later make_step or rollout gives the bits it would have given without it. */
 int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, double* dU_dp, int* ok, double* margin);
 int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev);
+
+/* Parametric sensitivities of the last solve's solution w.r.t. the vehicle and cost parameters theta: LTOMPC_NTHETA = 16
+ * columns, in this order and in natural units (the fields of ltompc_params):
+ *     mass, inertia_z, B_f, C_f, D_f, B_r, C_r, D_r, C_m, Cr_0, Cr_2, q_n, q_mu, q_B, r_du[0], r_du[1].
+ * Not covered: the geometry (length_f, length_r, width, gravity: it also enters the track constraints), q_vy, q_v,
+ * vref_scale, ptv and the friction-ellipse parameters.  A handle with ell_penalty > 0 or ptv != 0 is a usage error; soft
+ * track constraints (soft_rho > 0) are covered (the track constraints do not depend on theta).
+ *
+ * Definition: that of ltompc_get_sensitivities - the barrier problem at the final iterate with the final barrier parameter
+ * and table smoothing, the KKT matrix with delta_w = 0, the same instances (solver status SOLVED or ACCEPTABLE before the
+ * node-0 rule), dz/dtheta = -F_z^-1 F_theta.  theta enters every stage (the dynamics in both collocation
+ * equations and in the Lagrangian's mixed second derivatives, the weights in the cost gradient), so the initial state
+ * and input do not move: dX block 0 is 0, and dU_k = K_k dX_k + Kv_k dV_k + kff_k with a right-hand side of its own per column.
+ *   ok[b] equals ltompc_get_sensitivities' ok[b] bit for bit; every output of an instance with ok[b] = 0 is exactly 0.
+ *
+ * ltompc_get_param_sensitivities: host outputs in the caller's instance order, any may be NULL:
+ *   du0_dth  batch x 2 x 16;   dX_dth  batch x (N+1) x 8 x 16 (block 0 is 0);   dU_dth  batch x N x 2 x 16;   ok  batch ints.
+ * ltompc_param_sensitivities_dev: enqueues only, on the handle's stream: du0_dth_dev (batch x 2 x 16) and ok_dev (batch
+ *   ints), device pointers, either may be NULL.  The first request for any sensitivities on a handle allocates and
+ *   synchronises once, as for ltompc_sensitivities_dev; the first request for these allocates their own buffers the same way.
+ *
+ * Computed on the first request after a solve and cached until the next solve, set_initial_guess or set_initial_guess_dev;
+ * before any solve, after set_initial_guess and after rollout_dev a call is a usage error (the r_du columns need u_0 - u_prev
+ * of the solve: make_step keeps u_prev for them, the rollout does not).  The pass re-uses the re-linearisation and the
+ * delta_w = 0 factorisation of ltompc_get_sensitivities when that ran for the same solve (and the other way round) and
+ * writes buffers of its own only: neither pass changes the other's results, and every later make_step or rollout gives the
+ * bits it would have given without it. */
+int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok);
+int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev);
 
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:

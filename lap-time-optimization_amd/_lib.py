@@ -9,6 +9,10 @@ import numpy as np
 from ._build import LIB
 
 NX, NU = 8, 2
+# columns of ltompc_get_param_sensitivities (LTOMPC_NTHETA, include/ltompc.h): the ltompc_params fields, in this order
+THETA_NAMES = ("mass", "inertia_z", "B_f", "C_f", "D_f", "B_r", "C_r", "D_r", "C_m", "Cr_0", "Cr_2", "q_n", "q_mu", "q_B",
+               "r_du[0]", "r_du[1]")
+NTHETA = len(THETA_NAMES)
 NO_BOUND = 1.0e30
 STATUS_NAMES = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "numerical", 4: "stalled", 5: "infeasible"}
 
@@ -62,6 +66,8 @@ def lib() -> C.CDLL:
         L = C.CDLL(LIB)
         L.ltompc_last_error.restype = C.c_char_p
         L.ltompc_version.restype = C.c_char_p
+        L.ltompc_get_param_sensitivities.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+        L.ltompc_param_sensitivities_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

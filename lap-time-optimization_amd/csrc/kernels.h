@@ -22,6 +22,8 @@
 //   velocity.h    k_velocity_profile: the forward / backward speed-profile passes of src/velocity.py
 //   sensitivity.h k_sens_*: parametric sensitivities of the solution w.r.t. (x0, u_prev) at the final iterate
 //                 (ltompc_get_sensitivities): re-linearisation, head-less Riccati sweep at delta_w = 0, forward propagation
+//   param_sensitivity.h k_psens_*: the same w.r.t. the vehicle and cost parameters (ltompc_get_param_sensitivities): condensed
+//                 right-hand sides of the 16 columns, their backward recursion on the stored factorisation, forward pass
 #pragma once
 #include "layout.h"
 #include "linearise.h"
@@ -32,3 +34,4 @@
 #include "velocity.h"
 #include "rollout.h"
 #include "sensitivity.h"
+#include "param_sensitivity.h"

@@ -95,7 +95,15 @@ struct ltompc_solver {
   // parametric sensitivities (sensitivity.h, ltompc_get_sensitivities): the pass's own buffers, allocated on the first request.
   // sens_state: 0 no solve to differentiate, 1 a solve to differentiate, 2 du0 / ok / margin computed, 3 trajectories too
   int sens_state = 0;
-  bool sens_moved = false;  // the instances were moved (un-packed) after the pass: its stage / Riccati blocks are not where they were
+  bool sens_fact = false;  // the pass's stage / Riccati buffers hold the factorisation of the last solve at the instances' current slots
+  // parameter sensitivities (param_sensitivity.h, ltompc_get_param_sensitivities), on the same factorisation.
+  // psens_state: 0 not computed since the last solve, 1 du0 computed, 2 trajectories too
+  int psens_state = 0;
+  // u_prev of the last make_step in the caller's order (B x 2): W.uprev becomes u0 at its end, and the r_du columns need the
+  // Delta u_0 of the solve.  Kept by every make_step (one small copy); a rollout does not keep it (psens_uprev = false).
+  double* d_psens_uprev = nullptr;
+  bool psens_uprev = false;
+  double *d_psens_pv = nullptr, *d_psens_kf = nullptr, *d_psens_du0 = nullptr, *d_psens_dX = nullptr, *d_psens_dU = nullptr;
   Work Ws{};                // W with QP, RC, RS, LS -> the pass's buffers, si -> zeros
   Work* d_Ws = nullptr;
   int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
@@ -251,8 +259,23 @@ int ensure_unpacked(ltompc_solver* h) {
                        h->K.bd.ni, h->K.bd.nel, pass);
   HIPCHECK(hipGetLastError());
   h->packed = false;
-  if (h->sens_state >= 2) h->sens_moved = true;
+  h->sens_fact = false;  // (the sensitivity blocks are no longer at the instances' slots)
   return 0;
+}
+
+// The re-linearisation and head-less sweep of the sensitivity passes (sensitivity.h), shared by both: run once per solve, and
+// again only when the instances have moved since (same blocks, same bits, at their new slots).
+void sens_factorise(ltompc_solver* h) {
+  if (h->sens_fact) return;
+  const int N = h->N, Bp = h->Bp;
+  const bool ell = h->K.bd.nel > 0;  // the evaluation kernels the solve used (launch_iteration)
+  if (h->eval8) hipLaunchKernelGGL(k_sens_eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
+  else
+    hipLaunchKernelGGL(ell ? (h->ref_eval ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
+                           : (h->ref_eval ? k_sens_eval<BoundsRef, false> : k_sens_eval<BoundsAny, false>),
+                       dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
+  hipLaunchKernelGGL(k_sens_riccati8, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, h->Ws, (const int*)h->W.si, h->d_sens_inertia);
+  h->sens_fact = true;
 }
 
 // The sensitivity pass of the last solve (sensitivity.h), enqueued on the handle's stream: linearisation and head-less sweep
@@ -275,20 +298,11 @@ int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
     HIPCHECK(hipMemcpyAsync(h->d_Ws, &h->Ws, sizeof(Work), hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
   }
-  auto factorise = [&]() {
-    const bool ell = h->K.bd.nel > 0;  // the evaluation kernels the solve used (launch_iteration)
-    if (h->eval8) hipLaunchKernelGGL(k_sens_eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
-    else
-      hipLaunchKernelGGL(ell ? (h->ref_eval ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
-                             : (h->ref_eval ? k_sens_eval<BoundsRef, false> : k_sens_eval<BoundsAny, false>),
-                         dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
-    hipLaunchKernelGGL(k_sens_riccati8, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, h->Ws, (const int*)h->W.si, h->d_sens_inertia);
-  };
   if (h->sens_state == 1) {
-    factorise();
+    sens_factorise(h);
     hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, (const int*)h->d_sens_inertia, h->K.bd.ni, h->d_sens_du0,
                        h->d_sens_ok, h->d_sens_margin, (double*)nullptr, (double*)nullptr, (const int*)nullptr);
-    h->sens_state = 2, h->sens_moved = false;
+    h->sens_state = 2;
   }
   if (traj && h->sens_state == 2) {
     if (!h->d_sens_dX) {
@@ -296,10 +310,42 @@ int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
       rc |= h->dalloc(&h->d_sens_dU, (size_t)N * 2 * SENS_NP * B);
       if (rc) return -1;
     }
-    if (h->sens_moved) factorise();  // (same blocks, same bits, at the instances' new slots)
+    sens_factorise(h);
     hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, (const int*)h->d_sens_inertia, h->K.bd.ni, (double*)nullptr,
                        (int*)nullptr, (double*)nullptr, h->d_sens_dX, h->d_sens_dU, (const int*)h->d_sens_ok);
-    h->sens_state = 3, h->sens_moved = false;
+    h->sens_state = 3;
+  }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The parameter-sensitivity pass of the last solve (param_sensitivity.h): ok (and du0 / margin) of the pass above, whose
+// factorisation it shares, then the condensed right-hand sides of the 16 columns and their recursion.  Cached like the above.
+int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  if (sens_compute(h, false, who)) return -1;  // (the usage error before a solve comes from here)
+  if (!h->psens_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!h->d_psens_pv) {
+    int rc = h->dalloc(&h->d_psens_pv, (size_t)PV_NF * N * Bp, true);
+    rc |= h->dalloc(&h->d_psens_kf, (size_t)N * 2 * PS_NT * Bp, true);
+    rc |= h->dalloc(&h->d_psens_du0, (size_t)2 * PS_NT * B);
+    if (rc) return -1;
+  }
+  if (traj && !h->d_psens_dX) {
+    int rc = h->dalloc(&h->d_psens_dX, (size_t)(N + 1) * 8 * PS_NT * B);
+    rc |= h->dalloc(&h->d_psens_dU, (size_t)N * 2 * PS_NT * B);
+    if (rc) return -1;
+  }
+  if (h->psens_state == 0 || (traj && h->psens_state == 1)) {
+    sens_factorise(h);
+    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                       (const Consts*)h->d_K, (const Work*)h->d_W, h->d_psens_pv);
+    hipLaunchKernelGGL(k_psens_sweep, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1],
+                       (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
+                       traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
+    h->psens_state = traj ? 2 : 1;
   }
   HIPCHECK(hipGetLastError());
   return 0;
@@ -452,7 +498,7 @@ int ltompc_create(const ltompc_params* params, const ltompc_options* options, co
   rc |= h->dalloc(&W.QP, (size_t)QP_NF * (N + 1) * Bp, true), rc |= h->dalloc(&W.RC, (size_t)RC_NF * (N + 1) * Bp, true);
   rc |= h->dalloc(&W.RS, (size_t)RS_NF * N * Bp, true), rc |= h->dalloc(&W.SP, (size_t)SP_NF * N * Bp, true);
   rc |= h->dalloc(&W.LS, (size_t)3 * (options->n_linesearch + 1) * N * Bp, true);
-  rc |= h->dalloc(&W.x0, 8 * Bp), rc |= h->dalloc(&W.uprev, 2 * Bp);
+  rc |= h->dalloc(&W.x0, 8 * Bp), rc |= h->dalloc(&W.uprev, 2 * Bp), rc |= h->dalloc(&h->d_psens_uprev, 2 * Bp);
   rc |= h->dalloc(&W.st, (size_t)ST_NF * Bp), rc |= h->dalloc(&W.filt, (size_t)2 * FILTER_MAX * Bp);
   rc |= h->dalloc(&W.si, (size_t)SI_NF * Bp), rc |= h->dalloc(&W.active, (size_t)h->max_iter + 2);
   rc |= h->dalloc(&h->d_act[0], Bp), rc |= h->dalloc(&h->d_act[1], Bp), rc |= h->dalloc(&h->d_nact[0], 4), rc |= h->dalloc(&h->d_nact[1], 4);
@@ -548,7 +594,7 @@ int ltompc_set_initial_guess_dev(ltompc_handle h, const double* x0_dev) {
   if (!h || !x0_dev) return fail("ltompc_set_initial_guess: null argument");
   HIPCHECK(hipSetDevice(h->device));
   h->packed = false;  // a cold start overwrites the whole iterate: nothing to restore
-  h->sens_state = 0;  // (nor a solve to differentiate)
+  h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;  // (nor a solve to differentiate)
   hipLaunchKernelGGL(k_act_identity, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->d_orig, h->d_perm, h->B);  // (slot -> caller's index: identity again)
   hipLaunchKernelGGL(k_load_x0, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)nullptr, 0, 0);
   hipLaunchKernelGGL(k_zero_uprev, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -574,7 +620,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   const int B = h->B, N = h->N, Bp = h->Bp;
   const bool ell = h->K.bd.nel > 0;  // kernels instantiated with / without the friction-ellipse constraints
   Launcher L{h};
-  h->sens_state = 0;
+  h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;
   hipLaunchKernelGGL(k_load_x0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)(h->packed ? h->d_orig : nullptr),
                      h->K.o.resto_sticky, h->cold_next ? 0 : 1);
   if (h->cold_next) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -652,8 +698,10 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
     }
   }
   if (L.close()) return -1;
+  hipLaunchKernelGGL(k_psens_keep_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, h->d_psens_uprev, (const int*)(h->packed ? h->d_orig : nullptr));
   hipLaunchKernelGGL(k_store_u0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, u0_dev, (const int*)(h->packed ? h->d_orig : nullptr));
   HIPCHECK(hipGetLastError());
+  h->psens_uprev = true;
   h->last_launches = L.launches + 3;
   h->last_iterations = it + 1;
   h->sens_state = 1;
@@ -751,7 +799,7 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   if (h->eval8) return fail("ltompc_rollout: latency-mode handles (8-lanes-per-slot kernels) are not supported by the rollout");
   HIPCHECK(hipSetDevice(h->device));
   if (ensure_unpacked(h)) return -1;  // the rollout works in the caller's order (index-list compaction only)
-  h->sens_state = 0;
+  h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;
   constexpr int RING = ltompc_solver::ROLL_RING;
   if (!h->plant_streams[0]) {
     // low priority: the plant steps are not urgent, and the runtime keeps a pool of hardware queues per priority level, so
@@ -858,6 +906,7 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   h->roll_iterations = it + 1, h->roll_launches = L.launches;
   h->last_iterations = 0;  // (no per-iteration history after a rollout: ltompc_get_active_history returns 0)
   h->after_rollout = true;
+  h->psens_uprev = false;
   if (rc == 0) h->sens_state = 1;
   return rc;
 }
@@ -882,6 +931,29 @@ int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev) {
   if (sens_compute(h, false, "ltompc_sensitivities_dev")) return -1;
   const size_t B = h->B;
   if (du0_dp_dev) HIPCHECK(hipMemcpyAsync(du0_dp_dev, h->d_sens_du0, sizeof(double) * 2 * SENS_NP * B, hipMemcpyDeviceToDevice, h->stream));
+  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psens_compute(h, dX_dth || dU_dth, "ltompc_get_param_sensitivities")) return -1;
+  const size_t B = h->B, N = h->N;
+  if (du0_dth) HIPCHECK(hipMemcpyAsync(du0_dth, h->d_psens_du0, sizeof(double) * 2 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
+  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+  if (dX_dth) HIPCHECK(hipMemcpyAsync(dX_dth, h->d_psens_dX, sizeof(double) * (N + 1) * 8 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
+  if (dU_dth) HIPCHECK(hipMemcpyAsync(dU_dth, h->d_psens_dU, sizeof(double) * N * 2 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psens_compute(h, false, "ltompc_param_sensitivities_dev")) return -1;
+  const size_t B = h->B;
+  if (du0_dth_dev) HIPCHECK(hipMemcpyAsync(du0_dth_dev, h->d_psens_du0, sizeof(double) * 2 * PS_NT * B, hipMemcpyDeviceToDevice, h->stream));
   if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
   return 0;
 }

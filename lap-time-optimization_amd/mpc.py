@@ -114,6 +114,11 @@ class _MPC:
         ships a differentiator for the same quantities)."""
         return self._solver.sensitivities(trajectory)
 
+    def param_sensitivities(self, trajectory: bool = False):
+        """Parametric sensitivities of the last make_step's solution w.r.t. the vehicle and cost parameters
+        (BatchedMPC.param_sensitivities: mass, inertia, tyres, drivetrain, drag and the cost weights)."""
+        return self._solver.param_sensitivities(trajectory)
+
 
 class Controller:
     """src/mpc/controller.py:9-34: NLP weights, bounds and IPOPT settings; builds the device solver."""

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NX, NU, Options, Params, check, dptr, iptr, lib
+from ._lib import NTHETA, NX, NU, THETA_NAMES, Options, Params, check, dptr, iptr, lib
 from .tables import TrackTables
 
 KERNEL_CLASSES = ("eval", "riccati", "expand", "linesearch", "pick", "update", "riccati1", "step1")  # include/ltompc.h
@@ -32,6 +32,7 @@ class BatchedMPC:
         # after an initial guess.  None where the host does not see them (make_step_dev, rollout_dev).
         self._solved = None
         self._fb = None  # (du0_dx0, du0_duprev, ok) of that solve, fetched by the first feedback()
+        self._pfb = None  # du0_dtheta of that solve, fetched by the first feedback(theta=...)
         self._uprev_next = np.zeros((self.B, NU))
 
     def close(self):
@@ -50,7 +51,7 @@ class BatchedMPC:
         x0 = self._x(x0)
         check(lib().ltompc_set_initial_guess(self._h, dptr(x0)))
         self._solved, self._uprev_next = None, np.zeros((self.B, NU))
-        self._fb = None
+        self._fb = self._pfb = None
 
     def make_step(self, x0):
         x0 = self._x(x0)
@@ -58,7 +59,7 @@ class BatchedMPC:
         self.status = np.empty(self.B, dtype=np.int32)
         self.iters = np.empty(self.B, dtype=np.int32)
         self._solved = None
-        self._fb = None
+        self._fb = self._pfb = None
         check(lib().ltompc_make_step(self._h, dptr(x0), dptr(u0), iptr(self.status), iptr(self.iters)))
         if self._uprev_next is not None:
             self._solved = (x0.copy(), self._uprev_next.copy(), u0.copy())
@@ -72,17 +73,17 @@ class BatchedMPC:
     def set_initial_guess_dev(self, x0_ptr: int):
         check(lib().ltompc_set_initial_guess_dev(self._h, C.c_void_p(x0_ptr)))
         self._solved, self._uprev_next = None, np.zeros((self.B, NU))
-        self._fb = None
+        self._fb = self._pfb = None
 
     def make_step_dev(self, x0_ptr: int, u0_ptr: int):
         self._solved = self._uprev_next = None
-        self._fb = None
+        self._fb = self._pfb = None
         check(lib().ltompc_make_step_dev(self._h, C.c_void_p(x0_ptr), C.c_void_p(u0_ptr)))
 
     def rollout_dev(self, x_ptr: int, n_ticks: int, n_sub: int = 400, u_log_ptr: int = 0, status_log_ptr: int = 0, iters_log_ptr: int = 0):
         """Closed-loop rollout with free-running instances (ltompc_rollout_dev): n_ticks of make_step + plant step per instance."""
         self._solved = self._uprev_next = None
-        self._fb = None
+        self._fb = self._pfb = None
         check(lib().ltompc_rollout_dev(self._h, C.c_void_p(x_ptr), int(n_ticks), int(n_sub), C.c_void_p(u_log_ptr or None),
                                        C.c_void_p(status_log_ptr or None), C.c_void_p(iters_log_ptr or None)))
         it, ln = C.c_longlong(), C.c_longlong()
@@ -117,9 +118,51 @@ class BatchedMPC:
         """(x0, u_prev, u0) of the last make_step, (B,8), (B,2), (B,2); None after make_step_dev / rollout_dev / set_initial_guess."""
         return self._solved
 
-    def feedback(self, x, u_prev=None):
+    # ---- sensitivities w.r.t. the vehicle and cost parameters (ltompc_get_param_sensitivities, DESIGN.md §9.1) -------
+    def param_sensitivities(self, trajectory: bool = False):
+        """Derivatives of the last solve's solution w.r.t. theta = THETA_NAMES (mass, inertia_z, the Pacejka B/C/D of both axles,
+        C_m, Cr_0, Cr_2, q_n, q_mu, q_B, r_du[0], r_du[1]) in natural units, at its final iterate (include/ltompc.h).
+
+        Returns du0_dtheta (B,2,16), names (the 16 column names), ok (B,) bool (the same as sensitivities()' ok) and, with
+        trajectory=True, dX (B,N+1,8,16, block 0 is 0) and dU (B,N,2,16).  Where ok is False every output of the instance is 0."""
+        B, N = self.B, self.N
+        du0, ok = np.empty((B, NU, NTHETA)), np.empty(B, dtype=np.int32)
+        dX = np.empty((B, N + 1, NX, NTHETA)) if trajectory else None
+        dU = np.empty((B, N, NU, NTHETA)) if trajectory else None
+        check(lib().ltompc_get_param_sensitivities(self._h, dptr(du0), dptr(dX) if trajectory else None,
+                                                   dptr(dU) if trajectory else None, iptr(ok)))
+        out = dict(du0_dtheta=du0, names=THETA_NAMES, ok=ok != 0)
+        if trajectory:
+            out.update(dX=dX, dU=dU)
+        return out
+
+    def param_sensitivities_dev(self, du0_dth_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue the parameter sensitivities of the last solve into device buffers (B,2,16) doubles / (B,) int32, on the
+        handle's stream."""
+        check(lib().ltompc_param_sensitivities_dev(self._h, C.c_void_p(du0_dth_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    def theta(self):
+        """The handle's values of the 16 parameters of param_sensitivities(), in THETA_NAMES order."""
+        p = self.params
+        return np.array([getattr(p, n) for n in THETA_NAMES[:-2]] + [p.r_du[0], p.r_du[1]])
+
+    def feedback(self, x, u_prev=None, *, theta=None):
         """Tangential predictor of the last make_step: u0 + du0_dx0 (x - x0_solved) + du0_duprev (u_prev - u_prev_solved), and u0
-        where ok is False.  u_prev=None: the u_prev of that solve (no change in those directions)."""
+        where ok is False.  u_prev=None: the u_prev of that solve (no change in those directions).  theta: a dict name -> value
+        of parameters of param_sensitivities() (names in THETA_NAMES) that differ from the handle's; adds du0_dtheta (theta -
+        theta_solved).  theta=None: no change in those directions (and no parameter pass)."""
+        if theta is not None:
+            u = self.feedback(x, u_prev)
+            if self._pfb is None:  # one host copy per solve, not per call
+                self._pfb = self.param_sensitivities()["du0_dtheta"]
+            d = np.zeros(NTHETA)
+            cur = self.theta()
+            for name, v in theta.items():
+                if name not in THETA_NAMES:
+                    raise ValueError(f"feedback: unknown parameter {name!r} (one of {THETA_NAMES})")
+                j = THETA_NAMES.index(name)
+                d[j] = float(v) - cur[j]
+            return u + np.einsum("bij,j->bi", self._pfb, d)  # (rows with ok False are 0)
         if self._solved is None:
             raise _lib.LtompcError("feedback: no make_step to expand around (the last solve was not a host make_step, or an "
                                    "initial guess came after it)")
@@ -384,3 +427,14 @@ class SplitMPC:
         """BatchedMPC.sensitivities_dev of every part into its rows of (B,2,10) doubles / (B,) int32, each on its part's stream."""
         for p, (lo, hi) in zip(self.parts, self.bounds):
             p.sensitivities_dev(du0_dp_ptr + 8 * NU * 10 * lo if du0_dp_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def param_sensitivities(self, trajectory: bool = False):
+        """BatchedMPC.param_sensitivities of every part, stitched in the caller's order."""
+        r = [p.param_sensitivities(trajectory) for p in self.parts]
+        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+
+    def param_sensitivities_dev(self, du0_dth_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.param_sensitivities_dev of every part into its rows of (B,2,16) doubles / (B,) int32, each on its part's
+        stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.param_sensitivities_dev(du0_dth_ptr + 8 * NU * NTHETA * lo if du0_dth_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
