@@ -299,8 +299,8 @@ __device__ __forceinline__ void d_plant(const Consts& K, const double* x, const 
     for (int i = 0; i < 8; i++) y[i] += hs / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
   }
 }
-__global__ void k_plant(Consts K, int B, const double* __restrict__ x, const double* __restrict__ u, double dt,
-                        int n_sub, double* __restrict__ xn) {
+__global__ void __launch_bounds__(64) k_plant(Consts K, int B, const double* __restrict__ x, const double* __restrict__ u, double dt,
+                                              int n_sub, double* __restrict__ xn) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   double xb[8], y[8], uu[2] = {u[(size_t)b * 2], u[(size_t)b * 2 + 1]};

@@ -620,6 +620,13 @@ __device__ __forceinline__ void d_expand(const Consts& K, const Work& W, const i
       pi[i] = s;
     }
   }
+  // (pi must be complete here.  Its only use is in the multiplier block, so the compiler sank the products below the
+  //  linearisation: the 60 Riccati words and the steps were live across it instead of the 8 values of pi, and 77 VGPRs
+  //  went to scratch, their reloads waiting with vmcnt behind the stores of dT / dNU.  The empty asm takes pi as an
+  //  operand and makes the compiler produce it before the barrier; the arithmetic is unchanged.)
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(pi[0]), "+v"(pi[1]), "+v"(pi[2]), "+v"(pi[3]), "+v"(pi[4]), "+v"(pi[5]), "+v"(pi[6]), "+v"(pi[7]));
+#endif
   // (nothing may be scheduled across this point: without it the compiler hoists the ~100 loads of the linearisation
   //  above the costate, runs out of registers and spills the Riccati words one by one, each spill waiting for its load)
   __builtin_amdgcn_sched_barrier(0);

@@ -74,7 +74,7 @@ __global__ void k_roll_finish(Work W, Launch la, double* __restrict__ u_log, int
 }
 // PLANT -> READY / FINAL: the plant step of the instances that converged in one pass (its list; another stream, concurrent with
 // the solver)
-__global__ void k_roll_plant(Consts K, Work W, double* x_rm, double dt, int n_sub, const int* __restrict__ n_list, const int* __restrict__ list) {
+__global__ void __launch_bounds__(64) k_roll_plant(Consts K, Work W, double* x_rm, double dt, int n_sub, const int* __restrict__ n_list, const int* __restrict__ list) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n_list[0]) return;
   const int b = list[j];
