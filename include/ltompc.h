@@ -365,6 +365,27 @@ int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev);
 int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok);
 int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev);
 
+/* Per-instance vehicle and cost parameters.  Instance b may have its own row theta_b: the LTOMPC_NTHETA = 16
+ * values of ltompc_get_param_sensitivities' columns, in that order and in natural units.  Every other field of ltompc_params
+ * stays the handle's.  Instance b's NLP, plant step and sensitivities are then bit for bit those of a handle created with
+ * theta_b written into its params (handles of the same latency mode).
+ *
+ * ltompc_set_instance_params: theta is batch x 16 (host, caller's instance order); NULL goes back to the handle's params.
+ *   Every row is checked: all entries finite, mass > 0, inertia_z > 0, q_n, q_mu, q_B, r_du >= 0; a bad row is a usage error
+ *   that names the row and the column and leaves the handle unchanged.  A handle with ell_penalty > 0 or ptv != 0 (those terms
+ *   read the tyre and mass fields too) and the debug path LTOMPC_RICCATI=serial refuse rows with a usage error.
+ * ltompc_set_instance_params_dev: the same from a device array (batch x 16), enqueued on the handle's stream.  NOT checked.
+ *   The first set of either kind allocates two batch x 16 planes and synchronises once.
+ * ltompc_get_instance_params: the rows in effect (batch x 16): the handle's values in every row when none are set.
+ *
+ * A set takes effect at the next make_step, make_step_dev, rollout_dev or plant_step(_dev) and does not touch the warm start.
+ * The sensitivities (ltompc_get_sensitivities, ltompc_get_param_sensitivities) are those of the last solve, at the rows that
+ * solve used, also when rows were set after it.  ltompc_plant_step(_dev) and the rollout's plant steps use the rows;
+ * ltompc_slip_forces and the ltompc_test_* entry points always use the handle's params. */
+int ltompc_set_instance_params(ltompc_handle h, const double* theta);
+int ltompc_set_instance_params_dev(ltompc_handle h, const double* theta_dev);
+int ltompc_get_instance_params(ltompc_handle h, double* theta);
+
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:
  * index 0 eval (k_eval or k_eval8), 1 riccati (8 instances per wavefront), 2 expand (k_expand or k_expand8), 3 linesearch,

@@ -7,6 +7,7 @@ namespace ltompc {
 // ------------------------------------------------------------------------------------------ k_init
 // Cold: do_mpc set_initial_guess (every state slot = x0, inputs 0, multipliers 0).  Warm: keep the previous
 // primal/dual solution un-shifted (do_mpc), node 0 := new x0.  Slacks t = max(-h, bound_push), nu = mu/t.
+template <bool PI = false>
 __device__ __forceinline__ void d_init_slot(const Consts& K, const Work& W, const int k, const int b, const int cold) {
   const int N = W.N;
   double x0[8];
@@ -66,7 +67,7 @@ __device__ __forceinline__ void d_init_slot(const Consts& K, const Work& W, cons
     st[(size_t)ST_E0 * W.Bp + b] = 1e300, st[(size_t)ST_OBJ * W.Bp + b] = 0.0, st[(size_t)ST_TAU * W.Bp + b] = 0.99;
     st[(size_t)ST_THETA0 * W.Bp + b] = -1.0, st[(size_t)ST_THMAX * W.Bp + b] = 0.0, st[(size_t)ST_THMIN * W.Bp + b] = 0.0;
     st[(size_t)ST_DW * W.Bp + b] = 0.0, st[(size_t)ST_DW_TRY * W.Bp + b] = 0.0;
-    st[(size_t)ST_C00 * W.Bp + b] = cost_eval(K.p, K.T, eps, x0, false, nullptr, nullptr);
+    st[(size_t)ST_C00 * W.Bp + b] = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, x0, false, nullptr, nullptr);
     st[(size_t)ST_RHO * W.Bp + b] = rho, st[(size_t)ST_VIOL * W.Bp + b] = 0.0;
     for (int i = 0; i < SI_NF; i++)
       if (i != SI_PREV && (i != SI_STICKY || cold) && i != SI_PHASE && i != SI_TICKS && i != SI_FINAL) W.si[(size_t)i * W.Bp + b] = 0;
@@ -89,6 +90,15 @@ __global__ void k_init(const Consts* __restrict__ Kp, const Work* __restrict__ W
   int b = tid % W.Bp, k = tid / W.Bp;
   if (k >= W.N || b >= W.B) return;
   d_init_slot(K, W, k, b, cold);
+}
+// with per-instance vehicle and cost parameters (W.TH)
+__global__ void k_init_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, int cold) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int b = tid % W.Bp, k = tid / W.Bp;
+  if (k >= W.N || b >= W.B) return;
+  d_init_slot<true>(K, W, k, b, cold);
 }
 
 // ------------------------------------------------------------------------------------------ k_shift
@@ -279,22 +289,26 @@ __global__ void k_status_counts(Work W, int* __restrict__ counts, unsigned long 
 }
 
 // plant: classical RK4 with n_sub sub-steps, zero-order-hold input (do_mpc Simulator / CVODES stand-in)
-__device__ __forceinline__ void d_plant(const Consts& K, const double* x, const double* uu, const double dt, const int n_sub, double* y) {
+// PI: the vehicle parameters of column col of the [LTOMPC_NTHETA][Bp] plane th
+template <bool PI = false, class TP = const double*>
+__device__ __forceinline__ void d_plant(const Consts& K, const double* x, const double* uu, const double dt, const int n_sub, double* y,
+                                        const TP th = nullptr, const size_t Bp = 0, const size_t col = 0) {
+  decltype(auto) p = sel_params<PI>(K.p, th, Bp, col);
 #pragma unroll
   for (int i = 0; i < 8; i++) y[i] = x[i];
   const double hs = dt / n_sub;
   for (int s = 0; s < n_sub; s++) {
     double k1[8], k2[8], k3[8], k4[8], z[8];
-    rhs_val(K.p, K.T, 0.0, y, uu, k1);
+    rhs_val(p, K.T, 0.0, y, uu, k1);
 #pragma unroll
     for (int i = 0; i < 8; i++) z[i] = y[i] + 0.5 * hs * k1[i];
-    rhs_val(K.p, K.T, 0.0, z, uu, k2);
+    rhs_val(p, K.T, 0.0, z, uu, k2);
 #pragma unroll
     for (int i = 0; i < 8; i++) z[i] = y[i] + 0.5 * hs * k2[i];
-    rhs_val(K.p, K.T, 0.0, z, uu, k3);
+    rhs_val(p, K.T, 0.0, z, uu, k3);
 #pragma unroll
     for (int i = 0; i < 8; i++) z[i] = y[i] + hs * k3[i];
-    rhs_val(K.p, K.T, 0.0, z, uu, k4);
+    rhs_val(p, K.T, 0.0, z, uu, k4);
 #pragma unroll
     for (int i = 0; i < 8; i++) y[i] += hs / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
   }
@@ -309,6 +323,26 @@ __global__ void __launch_bounds__(64) k_plant(Consts K, int B, const double* __r
   d_plant(K, xb, uu, dt, n_sub, y);
 #pragma unroll
   for (int i = 0; i < 8; i++) xn[(size_t)b * 8 + i] = y[i];
+}
+// with per-instance vehicle parameters: th is a [LTOMPC_NTHETA][Bp] plane in the caller's instance order
+__global__ void __launch_bounds__(64) k_plant_pi(Consts K, const double* __restrict__ th, int Bp, int B, const double* __restrict__ x,
+                                                 const double* __restrict__ u, double dt, int n_sub, double* __restrict__ xn) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double xb[8], y[8], uu[2] = {u[(size_t)b * 2], u[(size_t)b * 2 + 1]};
+#pragma unroll
+  for (int i = 0; i < 8; i++) xb[i] = x[(size_t)b * 8 + i];
+  d_plant<true>(K, xb, uu, dt, n_sub, y, th, Bp, b);
+#pragma unroll
+  for (int i = 0; i < 8; i++) xn[(size_t)b * 8 + i] = y[i];
+}
+
+// [B][LTOMPC_NTHETA] rows (device, caller's order) -> columns 0 .. B-1 of a [LTOMPC_NTHETA][Bp] plane (ltompc_set_instance_params_dev)
+__global__ void k_theta_rows(const double* __restrict__ rows, double* __restrict__ th, int B, int Bp) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * LTOMPC_NTHETA) return;
+  const int b = t / LTOMPC_NTHETA, j = t % LTOMPC_NTHETA;
+  th[(size_t)j * Bp + b] = rows[t];
 }
 
 __global__ void k_slip_forces(Consts K, int B, const double* __restrict__ x, double* __restrict__ alpha,

@@ -62,7 +62,7 @@ struct Lin8 {  // what lane (g, i) holds of its slot after lin8()
   bool nl;
 };
 
-template <bool DUAL, bool EXPAND>
+template <bool DUAL, bool EXPAND, bool PI = false>
 __device__ __forceinline__ void lin8(const Consts& K, const Work& W, E8Lds& L, const int i, const int k, const int b,
                                      const double eps, Lin8& S) {
   const int N = W.N;
@@ -89,11 +89,11 @@ __device__ __forceinline__ void lin8(const Consts& K, const Work& W, E8Lds& L, c
   WAVE_SYNC();
   {
     double f[8];
-    rhs_derivs(K.p, K.T, eps, px, f, &L.r1[pt * 48], lam, hdt, &L.r2[pt * 36]);
+    rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, px, f, &L.r1[pt * 48], lam, hdt, &L.r2[pt * 36]);
 #pragma unroll
     for (int q = 0; q < 6; q++) L.r2[72 + pt * 8 + q] = f[q];
   }
-  S.cost = cost_eval(K.p, K.T, eps, S.xp, k == N - 1, pt ? &L.misc[0] : &L.vec[0], pt ? &L.r2[36] : &L.vec[8]);
+  S.cost = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, k == N - 1, pt ? &L.misc[0] : &L.vec[0], pt ? &L.r2[36] : &L.vec[8]);
   S.nl = (k + 1 <= N - 1);
   double hss[3] = {0, 0, 0}, hmm[3] = {0, 0, 0};
   if (S.nl) {
@@ -244,6 +244,7 @@ __device__ __forceinline__ void lin8(const Consts& K, const Work& W, E8Lds& L, c
 }
 
 // ------------------------------------------------------------------------------------------ k_eval8
+template <bool PI = false>
 __device__ __forceinline__ void d_eval8(const Consts& K, const Work& W, E8Lds& L, const int i, const int k, const int b,
                                         const bool live) {
   const int N = W.N;
@@ -256,7 +257,7 @@ __device__ __forceinline__ void d_eval8(const Consts& K, const Work& W, E8Lds& L
     __threadfence();  // the other lanes of the slot read what lane 0 has just stored
   }
   Lin8 S;
-  lin8<true, false>(K, W, L, i, k, b, eps, S);
+  lin8<true, false, PI>(K, W, L, i, k, b, eps, S);
   // ---- residual partials (IPOPT's E_mu ingredients), see d_eval
   {
     const double l1_i = PL(W.L1, i, k, N), l2_i = PL(W.L2, i, k, N);
@@ -276,9 +277,10 @@ __device__ __forceinline__ void d_eval8(const Consts& K, const Work& W, E8Lds& L
       const double ui = i == 0 ? S.u[0] : S.u[1];
       const double v0 = k ? PL(W.U, i, k - 1, N) : W.uprev[(size_t)i * W.Bp + b];
       const double du = ui - v0;
-      cost_u = K.p.r_du[i] * du * du;
-      double ru = S.dud + 2.0 * K.p.r_du[i] * du + hdt * (PL(W.L1, 6 + i, k, N) + PL(W.L2, 6 + i, k, N));
-      if (k + 1 < N) ru -= 2.0 * K.p.r_du[i] * (PL(W.U, i, k + 1, N) - ui);
+      const double rdu = inst_r_du<PI>(K.p, W, b, i);
+      cost_u = rdu * du * du;
+      double ru = S.dud + 2.0 * rdu * du + hdt * (PL(W.L1, 6 + i, k, N) + PL(W.L2, 6 + i, k, N));
+      if (k + 1 < N) ru -= 2.0 * rdu * (PL(W.U, i, k + 1, N) - ui);
       rd = fmax(rd, fabs(ru));
     }
     rd = grp_max(rd), rp = grp_max(rp), sm = grp_sum(sm);
@@ -371,15 +373,32 @@ __global__ void __launch_bounds__(64) k_eval8(const Consts* __restrict__ Kp, con
   if (!__any(live)) return;
   d_eval8(K, W, lds[g], i, k, b, live);
 }
+// with per-instance vehicle and cost parameters (W.TH)
+__global__ void __launch_bounds__(64) k_eval8_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, Launch la) {
+  const Consts& K = *Kp;  // K and W live in device memory: fields are fetched where they are used instead of
+  const Work& W = *Wp;    // occupying (spilled) SGPRs for the whole kernel
+  __shared__ E8Lds lds[8];
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int G8 = la.n_pad >> 3;
+  const int k = blockIdx.x / G8, j = (blockIdx.x % G8) * 8 + g;
+  const bool valid = j < la.nact[0];
+  const int b = la.act[valid ? j : 0];
+  const int* si = W.si;
+  const bool live = valid && !si[(size_t)SI_DONE * W.Bp + b] &&
+                    (la.force_eval || (!si[(size_t)SI_RETRY * W.Bp + b] && !si[(size_t)SI_SKIP_EVAL * W.Bp + b]));  // else: the blocks of the last launch are still valid
+  if (!__any(live)) return;
+  d_eval8<true>(K, W, lds[g], i, k, b, live);
+}
 
 // ------------------------------------------------------------------------------------------ k_expand8
+template <bool PI = false>
 __device__ __forceinline__ void d_expand8(const Consts& K, const Work& W, E8Lds& L, const int i, const int k, const int b,
                                           const bool live) {
   const int N = W.N;
   const double mu = W.st[(size_t)ST_MU * W.Bp + b], eps = W.st[(size_t)ST_EPS * W.Bp + b];
   const double tau = W.st[(size_t)ST_TAU * W.Bp + b], rho = W.st[(size_t)ST_RHO * W.Bp + b];
   Lin8 S;
-  lin8<false, true>(K, W, L, i, k, b, eps, S);
+  lin8<false, true, PI>(K, W, L, i, k, b, eps, S);
   double dxk[8], dxp[8], du[2];
 #pragma unroll
   for (int j = 0; j < 8; j++) dxk[j] = PL(W.dX, j, k, N + 1), dxp[j] = PL(W.dX, j, k + 1, N + 1);
@@ -416,7 +435,7 @@ __device__ __forceinline__ void d_expand8(const Consts& K, const Work& W, E8Lds&
     const double ui = i == 0 ? S.u[0] : S.u[1], dui = i == 0 ? du[0] : du[1];
     const double v0 = k ? PL(W.U, i, k - 1, N) : W.uprev[(size_t)i * W.Bp + b];
     const double dv0 = k ? PL(W.dU, i, k - 1, N) : 0.0;
-    gphid += 2.0 * K.p.r_du[i] * (ui - v0) * (dui - dv0);
+    gphid += 2.0 * inst_r_du<PI>(K.p, W, b, i) * (ui - v0) * (dui - dv0);
   }
   for_each_bound<BoundsAny>(K.p, [&](int m, int kind, int j, double sg, double val) {
     if (j != i) return;
@@ -476,6 +495,20 @@ __global__ void __launch_bounds__(64) k_expand8(const Consts* __restrict__ Kp, c
   const bool live = valid && !si[(size_t)SI_DONE * W.Bp + b] && si[(size_t)SI_STEP * W.Bp + b];  // else: no step this launch
   if (!__any(live)) return;
   d_expand8(K, W, lds[g], i, k, b, live);
+}
+__global__ void __launch_bounds__(64) k_expand8_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, Launch la) {
+  const Consts& K = *Kp;  // K and W live in device memory: fields are fetched where they are used instead of
+  const Work& W = *Wp;    // occupying (spilled) SGPRs for the whole kernel
+  __shared__ E8Lds lds[8];
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int G8 = la.n_pad >> 3;
+  const int k = blockIdx.x / G8, j = (blockIdx.x % G8) * 8 + g;
+  const bool valid = j < la.nact[0];
+  const int b = la.act[valid ? j : 0];
+  const int* si = W.si;
+  const bool live = valid && !si[(size_t)SI_DONE * W.Bp + b] && si[(size_t)SI_STEP * W.Bp + b];  // else: no step this launch
+  if (!__any(live)) return;
+  d_expand8<true>(K, W, lds[g], i, k, b, live);
 }
 
 }  // namespace ltompc

@@ -106,6 +106,44 @@ struct Work {
   gptr<double> BK;
   gptr<const int> orig;  // slot -> caller's index (identity while the instances are not packed)
 };
+// Work of the _pi kernels (per-instance vehicle and cost parameters, ltompc_set_instance_params): Work with one
+// field appended, TH, the rows theta of the last solve, a plane [LTOMPC_NTHETA][Bp] in the CALLER's instance order (indexed by
+// orig[b], as BK; pad columns hold the handle's values).  A struct of its own so that Work, and with it the argument layout and
+// the code of every existing kernel, stays as it was.  The device functions take `const Work&` and, instantiated with PI = true,
+// read TH through a cast back to WorkPI: they are called with PI = true by the _pi kernels only, whose Work IS a WorkPI.
+struct WorkPI : Work {
+  gptr<const double> TH;
+};
+
+// The params of instance b: the handle's with the 16 fields of theta (the columns of ltompc_get_param_sensitivities) taken from
+// column `col` of a [LTOMPC_NTHETA][Bp] plane.  Only the fields a caller reads are loaded, where it reads them (the copy is
+// scalarised), so a kernel keeps no 32 extra VGPRs live.
+template <class P>
+__device__ __forceinline__ ltompc_params theta_params(const ltompc_params& u, const P th, const size_t Bp, const size_t col) {
+  ltompc_params p = u;
+  const auto r = [&](const int j) { return th[(size_t)j * Bp + col]; };
+  p.mass = r(0), p.inertia_z = r(1), p.B_f = r(2), p.C_f = r(3), p.D_f = r(4), p.B_r = r(5), p.C_r = r(6), p.D_r = r(7);
+  p.C_m = r(8), p.Cr_0 = r(9), p.Cr_2 = r(10), p.q_n = r(11), p.q_mu = r(12), p.q_B = r(13), p.r_du[0] = r(14), p.r_du[1] = r(15);
+  return p;
+}
+// PI = false: the handle's params themselves (the existing kernels, unchanged); PI = true: those of column col of th.
+template <bool PI, class P>
+__device__ __forceinline__ decltype(auto) sel_params(const ltompc_params& u, const P th, const size_t Bp, const size_t col) {
+  if constexpr (PI) return theta_params(u, th, Bp, col);
+  else return (u);
+}
+// ... of the instance in slot b
+template <bool PI>
+__device__ __forceinline__ decltype(auto) inst_params(const ltompc_params& u, const Work& W, const int b) {
+  if constexpr (PI) return theta_params(u, static_cast<const WorkPI&>(W).TH, W.Bp, W.orig[b]);
+  else return (u);
+}
+// r_du[i] of instance b (i may be a lane-dependent index: read from the plane, not from a local copy)
+template <bool PI>
+__device__ __forceinline__ double inst_r_du(const ltompc_params& u, const Work& W, const int b, const int i) {
+  if constexpr (PI) return static_cast<const WorkPI&>(W).TH[(size_t)(14 + i) * W.Bp + W.orig[b]];
+  else return u.r_du[i];
+}
 
 // What changes from launch to launch (kernel argument; Work and Consts are read from device memory).  Compaction of the
 // unfinished instances: thread j of a launch works on instance act[j], j < nact[0] <= the launch width.  The list is

@@ -174,7 +174,7 @@ struct Slot {
   bool nl;
 };
 
-template <bool WITH_DUAL, class BP, bool ELL>
+template <bool WITH_DUAL, class BP, bool ELL, bool PI = false>
 __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, int k, int b, double eps, Slot& S) {
   const int N = W.N;
   const double hdt = K.o.t_step, rho = W.st[(size_t)ST_RHO * W.Bp + b];
@@ -191,12 +191,12 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
 #pragma unroll
   for (int i = 0; i < 36; i++) S.Hc[i] = 0.0, S.Hxp[i] = 0.0;
   double f1[8], f2[8], J[48];
-  rhs_derivs(K.p, K.T, eps, S.c, f1, J, l1, hdt, S.Hc);
+  rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, S.c, f1, J, l1, hdt, S.Hc);
 #pragma unroll
   for (int i = 0; i < 64; i++) S.E1[i] = 0.0, S.E2[i] = 0.0;
 #pragma unroll
   for (int i = 0; i < 48; i++) S.E1[i] = hdt * J[i];
-  rhs_derivs(K.p, K.T, eps, S.xp, f2, J, l2, hdt, S.Hxp);
+  rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, f2, J, l2, hdt, S.Hxp);
 #pragma unroll
   for (int i = 0; i < 48; i++) S.E2[i] = hdt * J[i];
   f1[6] = f2[6] = S.u[0], f1[7] = f2[7] = S.u[1];
@@ -208,7 +208,7 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
   }
 #pragma unroll
   for (int i = 0; i < 8; i++) S.gcost[i] = 0.0, S.gc0[i] = 0.0, S.gc1[i] = 0.0, S.gxp1[i] = 0.0, S.dcd[i] = 0.0;
-  S.cost = cost_eval(K.p, K.T, eps, S.xp, k == N - 1, S.gcost, S.Hxp);
+  S.cost = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, k == N - 1, S.gcost, S.Hxp);
 #pragma unroll
   for (int i = 0; i < 8; i++) S.gxp0[i] = S.gcost[i], S.dxd[i] = S.gcost[i];
   S.Du[0] = S.Du[1] = 0.0, S.gub0[0] = S.gub0[1] = 0.0, S.gub1[0] = S.gub1[1] = 0.0, S.dud[0] = S.dud[1] = 0.0;
@@ -476,7 +476,7 @@ __device__ __forceinline__ bool condense_slot(const Consts& K, const Slot& S, M8
 
 
 // ------------------------------------------------------------------------------------------ k_eval
-template <class BP, bool ELL>
+template <class BP, bool ELL, bool PI = false>
 __device__ __forceinline__ void d_eval(const Consts& K, const Work& W, const int k, const int b, const bool force) {
   const int N = W.N;
   if (W.si[(size_t)SI_DONE * W.Bp + b]) return;
@@ -486,7 +486,7 @@ __device__ __forceinline__ void d_eval(const Consts& K, const Work& W, const int
   const bool reinit = W.si[(size_t)SI_REINIT * W.Bp + b] != 0;  // the restoration phase starts with this evaluation
   if (reinit) reinit_slot<BP>(K, W, k, b);
   Slot S;
-  linearise_slot<true, BP, ELL>(K, W, k, b, eps, S);
+  linearise_slot<true, BP, ELL, PI>(K, W, k, b, eps, S);
   // ---- node block of x_{k+1}: complete after the linearisation, stored now so that its 52 registers are free during
   //      the elimination (stores issued late also cost more than their bandwidth: on gfx9 a later scratch reload
   //      has to wait for every store before it, vmcnt counts both)
@@ -524,9 +524,10 @@ __device__ __forceinline__ void d_eval(const Consts& K, const Work& W, const int
     for (int i = 0; i < 2; i++) {
       double v = k ? PL(W.U, i, k - 1, N) : W.uprev[(size_t)i * W.Bp + b];
       double du = S.u[i] - v;
-      cost += K.p.r_du[i] * du * du;
-      double ru = S.dud[i] + 2.0 * K.p.r_du[i] * du + hdt * (l1[6 + i] + l2[6 + i]);
-      if (k + 1 < N) ru -= 2.0 * K.p.r_du[i] * (PL(W.U, i, k + 1, N) - S.u[i]);
+      const double rdu = inst_r_du<PI>(K.p, W, b, i);
+      cost += rdu * du * du;
+      double ru = S.dud[i] + 2.0 * rdu * du + hdt * (l1[6 + i] + l2[6 + i]);
+      if (k + 1 < N) ru -= 2.0 * rdu * (PL(W.U, i, k + 1, N) - S.u[i]);
       rd = fmax(rd, fabs(ru));
     }
     rp = fmax(rp, S.rp_ineq), sm += S.smult;
@@ -592,10 +593,20 @@ __global__ void __launch_bounds__(64) k_eval(const Consts* __restrict__ Kp, cons
   if (k >= W.N || j >= la.nact[0]) return;
   d_eval<BP, ELL>(K, W, k, la.act[j], la.force_eval != 0);
 }
+// with per-instance vehicle and cost parameters (W.TH)
+template <class BP>
+__global__ void __launch_bounds__(64) k_eval_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, Launch la) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = tid % la.n_pad, k = tid / la.n_pad;
+  if (k >= W.N || j >= la.nact[0]) return;
+  d_eval<BP, false, true>(K, W, k, la.act[j], la.force_eval != 0);
+}
 
 
 // ------------------------------------------------------------------------------------------ k_expand
-template <class BP, bool ELL>
+template <class BP, bool ELL, bool PI = false>
 __device__ __forceinline__ void d_expand(const Consts& K, const Work& W, const int k, const int b) {
   const int N = W.N;
   if (W.si[(size_t)SI_DONE * W.Bp + b] || !W.si[(size_t)SI_STEP * W.Bp + b]) return;  // no step this launch
@@ -631,7 +642,7 @@ __device__ __forceinline__ void d_expand(const Consts& K, const Work& W, const i
   //  above the costate, runs out of registers and spills the Riccati words one by one, each spill waiting for its load)
   __builtin_amdgcn_sched_barrier(0);
   Slot S;
-  linearise_slot<false, BP, ELL>(K, W, k, b, eps, S);
+  linearise_slot<false, BP, ELL, PI>(K, W, k, b, eps, S);
   M8Blocks M8;
   factor_m8(S, M8);
   double dxk[8], dxp[8], du[2], dc[8];
@@ -690,7 +701,7 @@ __device__ __forceinline__ void d_expand(const Consts& K, const Work& W, const i
   for (int i = 0; i < 2; i++) {
     double v0 = k ? PL(W.U, i, k - 1, N) : W.uprev[(size_t)i * W.Bp + b];
     double dv0 = k ? PL(W.dU, i, k - 1, N) : 0.0;
-    gphid += 2.0 * K.p.r_du[i] * (S.u[i] - v0) * (du[i] - dv0);
+    gphid += 2.0 * inst_r_du<PI>(K.p, W, b, i) * (S.u[i] - v0) * (du[i] - dv0);
   }
 #pragma unroll
   for (int a = 0; a < 8; a++) gphid += S.gcost[a] * dxp[a];
@@ -777,6 +788,15 @@ __global__ void __launch_bounds__(64) k_expand(const Consts* __restrict__ Kp, co
   int j = tid % la.n_pad, k = tid / la.n_pad;
   if (k >= W.N || j >= la.nact[0]) return;
   d_expand<BP, ELL>(K, W, k, la.act[j]);
+}
+template <class BP>
+__global__ void __launch_bounds__(64) k_expand_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, Launch la) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = tid % la.n_pad, k = tid / la.n_pad;
+  if (k >= W.N || j >= la.nact[0]) return;
+  d_expand<BP, false, true>(K, W, k, la.act[j]);
 }
 
 }  // namespace ltompc

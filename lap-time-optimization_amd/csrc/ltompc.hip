@@ -108,6 +108,15 @@ struct ltompc_solver {
   Work* d_Ws = nullptr;
   int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
   double *d_sens_du0 = nullptr, *d_sens_margin = nullptr, *d_sens_dX = nullptr, *d_sens_dU = nullptr;
+  // per-instance vehicle and cost parameters (ltompc_set_instance_params): two [LTOMPC_NTHETA][Bp] planes in the
+  // caller's order, allocated on the first set.  d_th_pend: the rows in effect for the next solve and plant step (pi_pend: set);
+  // d_th_solve (WorkPI::TH): those of the last solve, copied from d_th_pend when a solve starts (pi_solve: it ran the _pi kernels),
+  // so that the sensitivities of that solve keep its rows whatever is set after it.
+  double *d_th_pend = nullptr, *d_th_solve = nullptr;
+  bool pi_pend = false, pi_solve = false;
+  bool pi_narrow = true;  // the narrow _pi Riccati kernels got their LDS limit (else the _pi path runs k_riccati8_pi at every width: same bits)
+  WorkPI Wpi{}, Wspi{};  // W and Ws with TH = d_th_solve (layout.h), and their device copies: the _pi kernels' Work
+  WorkPI *d_Wpi = nullptr, *d_Wspi = nullptr;
 
   // (P may be a gptr<T>: a global-address-space pointer in the device pass of the compiler, a plain one on the host)
   // work = true: an array that the kernels fill before they read it.  LTOMPC_POISON=1 (debug) fills those with 0xFF bytes
@@ -179,45 +188,97 @@ struct Launcher {
   }
 };
 
+// The kernels of an interior-point iteration: the uniform ones, or the _pi ones (per-instance vehicle and cost parameters,
+// DESIGN.md §10) with the WorkPI copies of W.  One launch sequence for both (launch_iteration).  The _pi kernels exist without
+// the friction ellipse only (ltompc_set_instance_params refuses it): their ELL selectors take no `ell`.
+template <bool PI> struct IterKernels;
+template <> struct IterKernels<false> {
+  static const Work* dev(const ltompc_solver* h) { return h->d_W; }
+  static const Work& val(const ltompc_solver* h) { return h->W; }
+  static int ric1_width(const ltompc_solver* h) { return h->ric1_width; }
+  static auto eval8() { return k_eval8; }
+  static auto expand8() { return k_expand8; }
+  static auto eval(const ltompc_solver* h, const bool ell) {
+    return ell ? (h->ref_eval ? k_eval<BoundsRef, true> : k_eval<BoundsAny, true>) : (h->ref_eval ? k_eval<BoundsRef, false> : k_eval<BoundsAny, false>);
+  }
+  static auto expand(const ltompc_solver* h, const bool ell) {
+    return ell ? (h->ref_expand ? k_expand<BoundsRef, true> : k_expand<BoundsAny, true>) : (h->ref_expand ? k_expand<BoundsRef, false> : k_expand<BoundsAny, false>);
+  }
+  static auto step1(const ltompc_solver* h, const bool ell) {
+    return ell ? (h->ref_step1 ? k_step1<BoundsRef, true> : k_step1<BoundsAny, true>) : (h->ref_step1 ? k_step1<BoundsRef, false> : k_step1<BoundsAny, false>);
+  }
+  static auto linesearch(const ltompc_solver* h, const bool ell) {
+    return ell ? (h->ref_ls ? k_linesearch<BoundsRef, true> : k_linesearch<BoundsAny, true>) : (h->ref_ls ? k_linesearch<BoundsRef, false> : k_linesearch<BoundsAny, false>);
+  }
+  static auto pick() { return k_pick; }
+  static auto riccati8() { return k_riccati8; }
+  static auto riccati1() { return k_riccati1; }
+  static auto riccati1q() { return k_riccati1q; }
+};
+template <> struct IterKernels<true> {
+  static const WorkPI* dev(const ltompc_solver* h) { return h->d_Wpi; }
+  static const WorkPI& val(const ltompc_solver* h) { return h->Wpi; }
+  static int ric1_width(const ltompc_solver* h) { return h->pi_narrow ? h->ric1_width : 0; }
+  static auto eval8() { return k_eval8_pi; }
+  static auto expand8() { return k_expand8_pi; }
+  static auto eval(const ltompc_solver* h, bool) { return h->ref_eval ? k_eval_pi<BoundsRef> : k_eval_pi<BoundsAny>; }
+  static auto expand(const ltompc_solver* h, bool) { return h->ref_expand ? k_expand_pi<BoundsRef> : k_expand_pi<BoundsAny>; }
+  static auto step1(const ltompc_solver* h, bool) { return h->ref_step1 ? k_step1_pi<BoundsRef> : k_step1_pi<BoundsAny>; }
+  static auto linesearch(const ltompc_solver* h, bool) { return h->ref_ls ? k_linesearch_pi<BoundsRef> : k_linesearch_pi<BoundsAny>; }
+  static auto pick() { return k_pick_pi; }
+  static auto riccati8() { return k_riccati8_pi; }
+  static auto riccati1() { return k_riccati1_pi; }
+  static auto riccati1q() { return k_riccati1q_pi; }
+};
+
 // The kernels of one interior-point iteration over the instances of `la` (make_step and the closed-loop rollout share it).
-int launch_iteration(ltompc_solver* h, Launcher& L, const Launch& la, const int it, const int n_launch, const int ls_width, const bool ell,
-                     const bool riccati_only) {
+template <bool PI>
+int launch_iteration_t(ltompc_solver* h, Launcher& L, const Launch& la, const int it, const int n_launch, const int ls_width, const bool ell,
+                       const bool riccati_only) {
+  using KS = IterKernels<PI>;
   const int N = h->N, np = la.n_pad;
-    if (h->eval8 ? L.run(0, k_eval8, N * np * 8, h->d_K, h->d_W, la) : L.run(0, ell ? (h->ref_eval ? k_eval<BoundsRef, true> : k_eval<BoundsAny, true>) : (h->ref_eval ? k_eval<BoundsRef, false> : k_eval<BoundsAny, false>), N * np, h->d_K, h->d_W, la)) return -1;
-    if (h->serial_riccati) {
+  const auto* Wd = KS::dev(h);
+  const auto& Wv = KS::val(h);
+    if (h->eval8 ? L.run(0, KS::eval8(), N * np * 8, h->d_K, Wd, la) : L.run(0, KS::eval(h, ell), N * np, h->d_K, Wd, la)) return -1;
+    if (!PI && h->serial_riccati) {  // (the _pi path never gets here: a handle with LTOMPC_RICCATI=serial refuses rows)
       if (L.run(1, k_riccati, np, h->d_K, h->d_W, la, it)) return -1;
     } else {
       // measured: letting the stragglers retry inside a launch (max_sweeps 4 when n_launch <= 256) finishes them in
       // fewer launches but doubles the time of every narrow launch: 193 ms vs 145 ms per tick at B = 8192
       const int max_sweeps = 1;
-      if (n_launch <= h->ric1_width) {
+      if (n_launch <= KS::ric1_width(h)) {
         if (n_launch <= h->ric1q_width) {  // four wavefronts per instance
           L.lds = ric1q_lds_bytes(N), L.block_threads = 256;
-          if (L.run(6, k_riccati1q, n_launch * 256, h->K, h->W, la, it, n_launch <= h->sweeps_width ? 4 : 1)) return -1;
+          if (L.run(6, KS::riccati1q(), n_launch * 256, h->K, Wv, la, it, n_launch <= h->sweeps_width ? 4 : 1)) return -1;
         } else {
           L.lds = ric1_lds_bytes(N);
-          if (L.run(6, k_riccati1, n_launch * 64, h->K, h->W, la, it, n_launch <= h->sweeps_width ? 4 : 1)) return -1;  // one wavefront per instance
+          if (L.run(6, KS::riccati1(), n_launch * 64, h->K, Wv, la, it, n_launch <= h->sweeps_width ? 4 : 1)) return -1;  // one wavefront per instance
         }
-      } else if (L.run(1, k_riccati8, np * 8, h->K, h->W, la, it, max_sweeps)) return -1;  // 8 lanes per instance
+      } else if (L.run(1, KS::riccati8(), np * 8, h->K, Wv, la, it, max_sweeps)) return -1;  // 8 lanes per instance
     }
     if (riccati_only) return 0;  // (make_step's last pass: only finalises the statuses, MAX_ITER)
-    if (h->eval8 ? L.run(2, k_expand8, N * np * 8, h->d_K, h->d_W, la) : L.run(2, ell ? (h->ref_expand ? k_expand<BoundsRef, true> : k_expand<BoundsAny, true>) : (h->ref_expand ? k_expand<BoundsRef, false> : k_expand<BoundsAny, false>), N * np, h->d_K, h->d_W, la)) return -1;
+    if (h->eval8 ? L.run(2, KS::expand8(), N * np * 8, h->d_K, Wd, la) : L.run(2, KS::expand(h, ell), N * np, h->d_K, Wd, la)) return -1;
     if (n_launch <= h->step1_width) {
       // one workgroup per instance does both line-search phases, the filter test and the update
       L.block_threads = 320;
-      if (L.run(7, ell ? (h->ref_step1 ? k_step1<BoundsRef, true> : k_step1<BoundsAny, true>) : (h->ref_step1 ? k_step1<BoundsRef, false> : k_step1<BoundsAny, false>), n_launch * 320, h->d_K, h->d_W, la)) return -1;
+      if (L.run(7, KS::step1(h, ell), n_launch * 320, h->d_K, Wd, la)) return -1;
     } else {
-      const auto kls = ell ? (h->ref_ls ? k_linesearch<BoundsRef, true> : k_linesearch<BoundsAny, true>) : (h->ref_ls ? k_linesearch<BoundsRef, false> : k_linesearch<BoundsAny, false>);
-      if (L.run(3, kls, N * np, h->d_K, h->d_W, la, 0, np)) return -1;
-      if (L.run(4, k_pick, np * 8, h->d_K, h->d_W, la, 0)) return -1;  // 8 lanes per instance
+      const auto kls = KS::linesearch(h, ell);
+      if (L.run(3, kls, N * np, h->d_K, Wd, la, 0, np)) return -1;
+      if (L.run(4, KS::pick(), np * 8, h->d_K, Wd, la, 0)) return -1;  // 8 lanes per instance
       if (h->K.o.n_linesearch > 1) {  // remaining step candidates, only for instances whose full step was rejected
         const int jw = np < ls_width ? np : ls_width;  // launch width of the second phase (longer lists are covered grid-stride)
-        if (L.run(3, kls, (h->K.o.n_linesearch - 1) * N * jw, h->d_K, h->d_W, la, 1, jw)) return -1;
-        if (L.run(4, k_pick, jw * 8, h->d_K, h->d_W, la, 1)) return -1;
+        if (L.run(3, kls, (h->K.o.n_linesearch - 1) * N * jw, h->d_K, Wd, la, 1, jw)) return -1;
+        if (L.run(4, KS::pick(), jw * 8, h->d_K, Wd, la, 1)) return -1;
       }
-      if (L.run(5, k_update, N * np, h->d_K, h->d_W, la)) return -1;
+      if (L.run(5, k_update, N * np, h->d_K, static_cast<const Work*>(Wd), la)) return -1;
     }
   return 0;
+}
+int launch_iteration(ltompc_solver* h, Launcher& L, const Launch& la, const int it, const int n_launch, const int ls_width, const bool ell,
+                     const bool riccati_only) {
+  return h->pi_solve ? launch_iteration_t<true>(h, L, la, it, n_launch, ls_width, ell, riccati_only)
+                     : launch_iteration_t<false>(h, L, la, it, n_launch, ls_width, ell, riccati_only);
 }
 
 int collect_profile(ltompc_solver* h) {
@@ -263,12 +324,23 @@ int ensure_unpacked(ltompc_solver* h) {
   return 0;
 }
 
+int sync_pi_work(ltompc_solver* h);
+
 // The re-linearisation and head-less sweep of the sensitivity passes (sensitivity.h), shared by both: run once per solve, and
 // again only when the instances have moved since (same blocks, same bits, at their new slots).
 void sens_factorise(ltompc_solver* h) {
   if (h->sens_fact) return;
   const int N = h->N, Bp = h->Bp;
   const bool ell = h->K.bd.nel > 0;  // the evaluation kernels the solve used (launch_iteration)
+  if (h->pi_solve) {  // (at each instance's rows of that solve, TH)
+    if (h->eval8) hipLaunchKernelGGL(k_sens_eval8_pi, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const WorkPI*)h->d_Wspi);
+    else
+      hipLaunchKernelGGL(h->ref_eval ? k_sens_eval_pi<BoundsRef> : k_sens_eval_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                         (const Consts*)h->d_K, (const WorkPI*)h->d_Wspi);
+    hipLaunchKernelGGL(k_sens_riccati8_pi, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, h->Wspi, (const int*)h->W.si, h->d_sens_inertia);
+    h->sens_fact = true;
+    return;
+  }
   if (h->eval8) hipLaunchKernelGGL(k_sens_eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
   else
     hipLaunchKernelGGL(ell ? (h->ref_eval ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
@@ -297,6 +369,7 @@ int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
     if (rc) return -1;
     HIPCHECK(hipMemcpyAsync(h->d_Ws, &h->Ws, sizeof(Work), hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
+    if (h->d_th_solve && sync_pi_work(h)) return -1;
   }
   if (h->sens_state == 1) {
     sens_factorise(h);
@@ -340,14 +413,68 @@ int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
   }
   if (h->psens_state == 0 || (traj && h->psens_state == 1)) {
     sens_factorise(h);
-    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
-                       (const Consts*)h->d_K, (const Work*)h->d_W, h->d_psens_pv);
-    hipLaunchKernelGGL(k_psens_sweep, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1],
-                       (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
-                       traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
+    if (h->pi_solve) {
+      hipLaunchKernelGGL(h->ref_eval ? k_psens_cond_pi<BoundsRef> : k_psens_cond_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                         (const Consts*)h->d_K, (const WorkPI*)h->d_Wpi, h->d_psens_pv);
+      hipLaunchKernelGGL(k_psens_sweep_pi, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Wspi, (const double*)h->d_psens_uprev,
+                         (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
+                         traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
+    } else {
+      hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                         (const Consts*)h->d_K, (const Work*)h->d_W, h->d_psens_pv);
+      hipLaunchKernelGGL(k_psens_sweep, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1],
+                         (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
+                         traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
+    }
     h->psens_state = traj ? 2 : 1;
   }
   HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The _pi kernels' Work (W, and Ws once the sensitivity pass has made it, with TH = d_th_solve), here and on the device.
+int sync_pi_work(ltompc_solver* h) {
+  static_cast<Work&>(h->Wpi) = h->W, h->Wpi.TH = (gptr<const double>)h->d_th_solve;
+  HIPCHECK(hipMemcpyAsync(h->d_Wpi, &h->Wpi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream));
+  if (h->d_Ws) {
+    static_cast<Work&>(h->Wspi) = h->Ws, h->Wspi.TH = (gptr<const double>)h->d_th_solve;
+    HIPCHECK(hipMemcpyAsync(h->d_Wspi, &h->Wspi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// theta of the handle's params (the order of ltompc_get_param_sensitivities' columns)
+void theta_of(const ltompc_params& p, double* t) {
+  const double v[LTOMPC_NTHETA] = {p.mass, p.inertia_z, p.B_f, p.C_f, p.D_f, p.B_r, p.C_r, p.D_r, p.C_m, p.Cr_0, p.Cr_2,
+                                   p.q_n, p.q_mu, p.q_B, p.r_du[0], p.r_du[1]};
+  std::memcpy(t, v, sizeof v);
+}
+
+// Per-instance rows: the checks every set makes, and the two planes on the first set (every column = the handle's values).
+int theta_prepare(ltompc_solver* h, const char* who) {
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  if (h->serial_riccati) return fail(std::string(who) + ": not available with LTOMPC_RICCATI=serial");
+  if (h->d_th_pend) return 0;
+  const size_t Bp = h->Bp;
+  std::vector<double> plane((size_t)LTOMPC_NTHETA * Bp);
+  double t[LTOMPC_NTHETA];
+  theta_of(h->K.p, t);
+  for (int j = 0; j < LTOMPC_NTHETA; j++)
+    for (size_t b = 0; b < Bp; b++) plane[j * Bp + b] = t[j];
+  if (h->dalloc(&h->d_th_pend, plane.size()) || h->dalloc(&h->d_th_solve, plane.size())) return -1;
+  HIPCHECK(hipMemcpyAsync(h->d_th_pend, plane.data(), plane.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->d_th_solve, plane.data(), plane.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (h->dalloc(&h->d_Wpi, 1) || h->dalloc(&h->d_Wspi, 1)) return -1;
+  return sync_pi_work(h);
+}
+
+// Start of a solve: the rows set become the solve's rows (W.TH).  Nothing at all on a handle that never had rows.
+int commit_theta(ltompc_solver* h) {
+  if (h->pi_pend)
+    HIPCHECK(hipMemcpyAsync(h->d_th_solve, h->d_th_pend, sizeof(double) * LTOMPC_NTHETA * h->Bp, hipMemcpyDeviceToDevice, h->stream));
+  h->pi_solve = h->pi_pend;
   return 0;
 }
 
@@ -479,6 +606,13 @@ int ltompc_create(const ltompc_params* params, const ltompc_options* options, co
       (void)hipGetLastError();
       h->ric1_width = 0;
     }
+    // (the _pi forms apart: a failure there must not change the uniform path)
+    if (h->ric1_width > 0 &&
+        (hipFuncSetAttribute(reinterpret_cast<const void*>(k_riccati1_pi), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+         hipFuncSetAttribute(reinterpret_cast<const void*>(k_riccati1q_pi), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)) {
+      (void)hipGetLastError();
+      h->pi_narrow = false;
+    }
   }
   const size_t N = h->N, Bp = h->Bp;
   const int ni = h->K.bd.ni;
@@ -598,6 +732,7 @@ int ltompc_set_initial_guess_dev(ltompc_handle h, const double* x0_dev) {
   hipLaunchKernelGGL(k_act_identity, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->d_orig, h->d_perm, h->B);  // (slot -> caller's index: identity again)
   hipLaunchKernelGGL(k_load_x0, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)nullptr, 0, 0);
   hipLaunchKernelGGL(k_zero_uprev, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W);
+  // (always the uniform k_init: the next make_step or rollout re-initialises every slot with the rows it solves with)
   hipLaunchKernelGGL(k_init, dim3((h->N * h->Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, 1);
   HIPCHECK(hipGetLastError());
   h->cold_next = true;  // the next make_step starts from this guess
@@ -621,6 +756,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   const bool ell = h->K.bd.nel > 0;  // kernels instantiated with / without the friction-ellipse constraints
   Launcher L{h};
   h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;
+  if (commit_theta(h)) return -1;
   hipLaunchKernelGGL(k_load_x0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)(h->packed ? h->d_orig : nullptr),
                      h->K.o.resto_sticky, h->cold_next ? 0 : 1);
   if (h->cold_next) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -628,7 +764,8 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 0);
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 1);
   }
-  hipLaunchKernelGGL(k_init, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, h->cold_next ? 1 : 0);
+  if (h->pi_solve) hipLaunchKernelGGL(k_init_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, h->cold_next ? 1 : 0);
+  else hipLaunchKernelGGL(k_init, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, h->cold_next ? 1 : 0);
   HIPCHECK(hipMemsetAsync(h->W.active, 0, sizeof(int) * ((size_t)h->max_iter + 2), h->stream));
   HIPCHECK(hipMemsetAsync(h->W.ls_count, 0, 2 * sizeof(int), h->stream));
   h->cold_next = false, h->after_rollout = false;
@@ -800,6 +937,7 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   HIPCHECK(hipSetDevice(h->device));
   if (ensure_unpacked(h)) return -1;  // the rollout works in the caller's order (index-list compaction only)
   h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;
+  if (commit_theta(h)) return -1;
   constexpr int RING = ltompc_solver::ROLL_RING;
   if (!h->plant_streams[0]) {
     // low priority: the plant steps are not urgent, and the runtime keeps a pool of hardware queues per priority level, so
@@ -852,7 +990,9 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
     ROLLCHECK(hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), h->stream));
     hipLaunchKernelGGL(k_roll_mark, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, (const double*)x_dev, h->K.o.resto_sticky,
                        (first && h->cold_next) ? 1 : 0);  // (after set_initial_guess there is no solve before this one to take stock of)
-    hipLaunchKernelGGL(k_roll_init, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, la, (first && h->cold_next) ? 1 : 0);
+    if (h->pi_solve)
+      hipLaunchKernelGGL(k_roll_init_pi, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, la, (first && h->cold_next) ? 1 : 0);
+    else hipLaunchKernelGGL(k_roll_init, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, la, (first && h->cold_next) ? 1 : 0);
     la.force_eval = 0;
     if (launch_iteration(h, L, la, -1, n_launch, ls_width, ell, false) < 0) { rc = -1; break; }  // (-1: no per-iteration count of unfinished instances, a make_step facility)
     hipLaunchKernelGGL(k_roll_finish, dim3((np + 63) / 64), dim3(64), 0, h->stream, h->W, la, u_log_dev, status_log_dev, iters_log_dev, n_ticks,
@@ -867,6 +1007,10 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
       hipStream_t ps = h->plant_streams[it % h->n_plant_streams];
       ROLLCHECK(hipEventRecord(h->ev_fin[slot], h->stream));
       ROLLCHECK(hipStreamWaitEvent(ps, h->ev_fin[slot], 0));
+      if (h->pi_solve)
+        hipLaunchKernelGGL(k_roll_plant_pi, dim3((n_launch + 63) / 64), dim3(64), 0, ps, h->K, h->Wpi, x_dev, h->K.o.t_step, n_sub, (const int*)(d_cnt + 1),
+                           (const int*)d_list);
+      else
       hipLaunchKernelGGL(k_roll_plant, dim3((n_launch + 63) / 64), dim3(64), 0, ps, h->K, h->W, x_dev, h->K.o.t_step, n_sub, (const int*)(d_cnt + 1),
                          (const int*)d_list);
       ROLLCHECK(hipEventRecord(h->ev_done[slot], ps));
@@ -958,6 +1102,58 @@ int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok
   return 0;
 }
 
+int ltompc_set_instance_params(ltompc_handle h, const double* theta) {
+  static const char* names[LTOMPC_NTHETA] = {"mass", "inertia_z", "B_f", "C_f", "D_f", "B_r", "C_r", "D_r", "C_m", "Cr_0", "Cr_2",
+                                             "q_n", "q_mu", "q_B", "r_du[0]", "r_du[1]"};
+  if (!h) return fail("null handle");
+  if (!theta) {
+    h->pi_pend = false;
+    return 0;
+  }
+  const char* who = "ltompc_set_instance_params";
+  for (int b = 0; b < h->B; b++)
+    for (int j = 0; j < LTOMPC_NTHETA; j++) {
+      const double v = theta[(size_t)b * LTOMPC_NTHETA + j];
+      const char* why = !std::isfinite(v) ? "is not finite" : (j < 2 && !(v > 0.0)) ? "must be > 0" : (j >= 11 && !(v >= 0.0)) ? "must be >= 0" : nullptr;
+      if (why) return fail(std::string(who) + ": row " + std::to_string(b) + ", column " + std::to_string(j) + " (" + names[j] + ") " + why);
+    }
+  HIPCHECK(hipSetDevice(h->device));
+  if (theta_prepare(h, who)) return -1;
+  const size_t Bp = h->Bp;
+  std::vector<double> plane((size_t)LTOMPC_NTHETA * h->B);  // (columns 0 .. B-1; the pad columns keep the handle's values)
+  for (int b = 0; b < h->B; b++)
+    for (int j = 0; j < LTOMPC_NTHETA; j++) plane[(size_t)j * h->B + b] = theta[(size_t)b * LTOMPC_NTHETA + j];
+  HIPCHECK(hipMemcpy2DAsync(h->d_th_pend, Bp * sizeof(double), plane.data(), h->B * sizeof(double), h->B * sizeof(double), LTOMPC_NTHETA,
+                            hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->pi_pend = true;
+  return 0;
+}
+
+int ltompc_set_instance_params_dev(ltompc_handle h, const double* theta_dev) {
+  if (!h) return fail("null handle");
+  if (!theta_dev) {
+    h->pi_pend = false;
+    return 0;
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  if (theta_prepare(h, "ltompc_set_instance_params_dev")) return -1;
+  hipLaunchKernelGGL(k_theta_rows, dim3((h->B * LTOMPC_NTHETA + 255) / 256), dim3(256), 0, h->stream, theta_dev, h->d_th_pend, h->B, h->Bp);
+  HIPCHECK(hipGetLastError());
+  h->pi_pend = true;
+  return 0;
+}
+
+int ltompc_get_instance_params(ltompc_handle h, double* theta) {
+  if (!h || !theta) return fail("ltompc_get_instance_params: null argument");
+  if (!h->pi_pend) {
+    for (int b = 0; b < h->B; b++) theta_of(h->K.p, theta + (size_t)b * LTOMPC_NTHETA);
+    return 0;
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  return planes_to_host(h, h->d_th_pend, LTOMPC_NTHETA, 1, theta);
+}
+
 int ltompc_rollout_info(ltompc_handle h, long long* iterations, long long* launches) {
   if (!h) return fail("null handle");
   if (iterations) *iterations = h->roll_iterations;
@@ -1011,7 +1207,10 @@ int ltompc_plant_step_dev(ltompc_handle h, const double* x_dev, const double* u_
   if (!h || !x_dev || !u_dev || !x_next_dev) return fail("ltompc_plant_step: null argument");
   if (n_sub < 1) return fail("ltompc_plant_step: n_sub must be >= 1");
   HIPCHECK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_plant, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, h->B, x_dev, u_dev, h->K.o.t_step, n_sub, x_next_dev);
+  if (h->pi_pend)  // (the rows in effect: those set last)
+    hipLaunchKernelGGL(k_plant_pi, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, (const double*)h->d_th_pend, h->Bp, h->B, x_dev, u_dev,
+                       h->K.o.t_step, n_sub, x_next_dev);
+  else hipLaunchKernelGGL(k_plant, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, h->B, x_dev, u_dev, h->K.o.t_step, n_sub, x_next_dev);
   HIPCHECK(hipGetLastError());
   return 0;
 }

@@ -143,7 +143,7 @@ __device__ __forceinline__ void cost_theta(const ltompc_params& p, const int j, 
 //   bc = M8^-1 (-G2t - 2 E2 G1t),  b = 2 (E1 bc + G1t),  w = Hc bc + gct,
 //   q = Ac^T w = (2I - 4E2)^T M8^-T w,  r = Bc^T w = -h [(I + 2E2)^T M8^-T w]_{delta, T},  qx = gxt
 // G1t, G2t have rows vx, vy, r only, so bc and b have rows 0..5 only.
-template <class BP>
+template <class BP, bool PI = false>
 __device__ __forceinline__ void d_psens_cond(const Consts& K, const Work& W, const int k, const int b, double* __restrict__ PV) {
   const int N = W.N;
   const double hdt = K.o.t_step;
@@ -160,8 +160,8 @@ __device__ __forceinline__ void d_psens_cond(const Consts& K, const Work& W, con
 #pragma unroll 1
     for (int j = 0; j < PS_NDYN; j++) {
       double f1[3], g1[5], f2[3], g2[5];
-      theta_jet(K.p, j, c, l1, f1, g1);
-      theta_jet(K.p, j, xp, l2, f2, g2);
+      theta_jet(inst_params<PI>(K.p, W, b), j, c, l1, f1, g1);
+      theta_jet(inst_params<PI>(K.p, W, b), j, xp, l2, f2, g2);
       double* out = PV + (size_t)pv_base(j) * N * W.Bp;  // (this column's planes)
 #pragma unroll
       for (int i = 0; i < 3; i++) PL(out, PV_b + 3 + i, k, N) = hdt * f1[i], PL(out, PV_q + i, k, N) = hdt * f2[i];
@@ -173,7 +173,7 @@ __device__ __forceinline__ void d_psens_cond(const Consts& K, const Work& W, con
 #pragma unroll 1
     for (int j = PS_NDYN; j < PS_NDYN + 3; j++) {
       double g[8];
-      cost_theta(K.p, j, xp, k == N - 1, g);
+      cost_theta(inst_params<PI>(K.p, W, b), j, xp, k == N - 1, g);
       double* out = PV + (size_t)pv_qx(j) * N * W.Bp;
 #pragma unroll
       for (int a = 0; a < 8; a++) PL(out, a, k, N) = g[a];
@@ -188,12 +188,12 @@ __device__ __forceinline__ void d_psens_cond(const Consts& K, const Work& W, con
     for (int i = 0; i < 8; i++) lam[i] = PL(W.L1, i, k, N);
 #pragma unroll
     for (int i = 0; i < 36; i++) S.Hc[i] = 0.0;
-    rhs_derivs(K.p, K.T, eps, c, f, J, lam, hdt, S.Hc);
+    rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, c, f, J, lam, hdt, S.Hc);
 #pragma unroll
     for (int i = 0; i < 64; i++) S.E1[i] = 0.0, S.E2[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < 48; i++) S.E1[i] = hdt * J[i];
-    rhs_derivs(K.p, K.T, eps, xp, f, J, nullptr, 0.0, nullptr);
+    rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, xp, f, J, nullptr, 0.0, nullptr);
 #pragma unroll
     for (int i = 0; i < 48; i++) S.E2[i] = hdt * J[i];
 #pragma unroll
@@ -258,6 +258,16 @@ __global__ void __launch_bounds__(64) k_psens_cond(const Consts* __restrict__ Kp
   if (k >= W.N || b >= W.B) return;
   d_psens_cond<BP>(K, W, k, b, PV);
 }
+// with per-instance vehicle and cost parameters (W.TH)
+template <class BP>
+__global__ void __launch_bounds__(64) k_psens_cond_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, double* __restrict__ PV) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = tid % W.Bp, k = tid / W.Bp;
+  if (k >= W.N || b >= W.B) return;
+  d_psens_cond<BP, true>(K, W, k, b, PV);
+}
 
 // ------------------------------------------------------------------------------------------ k_psens_sweep
 // Columns c0 = 8 * blockIdx.y + col.  Per stage k (N-1 .. 0), with P, Pxv of stage k+1 and K, Kv of stage k as stored by the
@@ -272,7 +282,7 @@ struct PsensLds {
   double x[8][8 * PS_NC];  // [g][row * 8 + col]: b, Pb and dX exchanged between the rows
 };
 
-template <int H>
+template <int H, bool PI = false>
 __device__ __forceinline__ void d_psens_sweep(const Work& W, PsensLds& L, const double r0, const double r1, const double* __restrict__ uprev,
                                               const double* __restrict__ PV,
                                               const int* __restrict__ ok_in, double* __restrict__ KF, double* __restrict__ du0,
@@ -284,7 +294,8 @@ __device__ __forceinline__ void d_psens_sweep(const Work& W, PsensLds& L, const 
   const int N = W.N;
   const size_t ob = W.orig[b];
   const bool okk = ok_in[ob] != 0;
-  const double r2[2] = {2.0 * r0, 2.0 * r1};
+  const gptr<const double> th = PI ? static_cast<const WorkPI&>(W).TH : nullptr;  // (PI: r_du of the instance's row, r0 / r1 unused)
+  const double r2[2] = {2.0 * (PI ? th[(size_t)14 * W.Bp + ob] : r0), 2.0 * (PI ? th[(size_t)15 * W.Bp + ob] : r1)};
   constexpr int C0 = H * PS_NC;
   // row i of a column's vector at slot k (compile-time zero where the column has none)
   auto vq = [&](const int c, const int k) { return C0 + c < PS_NDYN ? PL(PV, pv_base(C0 + c) + PV_q + i, k, N) : 0.0; };
@@ -454,6 +465,15 @@ __global__ void __launch_bounds__(64) k_psens_sweep(Work W, double r0, double r1
   __shared__ PsensLds L;
   if (blockIdx.y == 0) d_psens_sweep<0>(W, L, r0, r1, uprev, PV, ok_in, KF, du0, dXo, dUo);
   else d_psens_sweep<1>(W, L, r0, r1, uprev, PV, ok_in, KF, du0, dXo, dUo);
+}
+// with per-instance r_du (W.TH)
+__global__ void __launch_bounds__(64) k_psens_sweep_pi(WorkPI W, const double* __restrict__ uprev, const double* __restrict__ PV,
+                                                    const int* __restrict__ ok_in,
+                                                    double* __restrict__ KF, double* __restrict__ du0, double* __restrict__ dXo,
+                                                    double* __restrict__ dUo) {
+  __shared__ PsensLds L;
+  if (blockIdx.y == 0) d_psens_sweep<0, true>(W, L, 0.0, 0.0, uprev, PV, ok_in, KF, du0, dXo, dUo);
+  else d_psens_sweep<1, true>(W, L, 0.0, 0.0, uprev, PV, ok_in, KF, du0, dXo, dUo);
 }
 
 }  // namespace ltompc

@@ -30,6 +30,7 @@ __device__ __forceinline__ int node0_rule(const ltompc_options& o, const double 
 // units of the penalty scale), filter and regularisation history dropped.  This launch does no sweep for the instance.
 // Used by the penalty escalation of the restoration phase and by the fallback of a tuned warm start; d_pick has the same
 // block for the entry of the restoration phase.
+template <bool PI = false>
 __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work& W, const int b, const double rho) {
   double* st = W.st;
   int* si = W.si;
@@ -42,7 +43,7 @@ __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work&
     double x0[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
-    STD(ST_C00) = cost_eval(K.p, K.T, eps, x0, false, nullptr, nullptr);
+    STD(ST_C00) = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, x0, false, nullptr, nullptr);
   }
   STI(SI_REINIT) = 1;
   STI(SI_NFILT) = 0, STD(ST_THETA0) = -1.0;
@@ -377,6 +378,7 @@ __global__ void __launch_bounds__(64) k_riccati(const Consts* __restrict__ Kp, c
 // (lane = g + 8 i) that own it in d_riccati8 / d_riccati1: lane i reduces the partials of the intervals k = i, i + 8, ...;
 // the sums over k are formed in the order k = 0..N-1 by every lane (identical to the serial kernel, so that all three
 // produce the same bits).  Returns false when no lane of the wavefront has a sweep to do.
+template <bool PI = false>
 __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const int i, const int b, const bool valid,
                                         const int active_slot, bool& live, bool& retry, double& mu) {
   const int N = W.N;
@@ -472,7 +474,7 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
         STI(SI_STEP) = 0, STI(SI_SKIP_EVAL) = 0;
       }
       if (escalate) {
-        restart_from_primal(K, W, b, fmin(rho * o.resto_rho_factor, o.resto_rho_max));
+        restart_from_primal<PI>(K, W, b, fmin(rho * o.resto_rho_factor, o.resto_rho_max));
         STI(SI_NRESTO) += 1;
       }
     }
@@ -525,7 +527,7 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
       STD(ST_TAU) = fmax(o.tau_min, 1.0 - mu * iS);
       if (fallback) {
         STI(SI_FBARMED) = 0, STI(SI_NFALLBACK) += 1;
-        restart_from_primal(K, W, b, rho);
+        restart_from_primal<PI>(K, W, b, rho);
       }
     }
     if (fallback || (stuck && !recoverable)) live = false;
@@ -559,7 +561,7 @@ struct FwdRegs {
 // SENS (sensitivity.h): the head-less factorisation at the final iterate - no head, delta_w = 0, one sweep, no schedule,
 // no status writes, no rollout; sens_live selects the instances whose gains are stored, sens_inertia[b] gets 1 when every
 // stage's Huu passed the inertia test.  The solver's instantiation (SENS = false) is unchanged.
-template <bool SENS = false>
+template <bool SENS = false, bool PI = false>
 __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLds& L, const int g, const int i, const int b,
                                            const bool valid, const int active_slot, const int max_sweeps, const bool sens_live = false,
                                            int* sens_inertia = nullptr) {
@@ -576,11 +578,11 @@ __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLd
       return;
     }
   } else {
-    if (!d_head8(K, W, i, b, valid, active_slot, live, retry, mu)) return;
+    if (!d_head8<PI>(K, W, i, b, valid, active_slot, live, retry, mu)) return;
   }
   // ---- backward sweep (whole wave in lock-step; an instance whose Huu fails retries with a larger delta_w,
   //      the others recompute the same numbers)
-  const double r2[2] = {2.0 * K.p.r_du[0], 2.0 * K.p.r_du[1]};
+  const double r2[2] = {2.0 * inst_r_du<PI>(K.p, W, b, 0), 2.0 * inst_r_du<PI>(K.p, W, b, 1)};
   const double psc = pen_scale(STD(ST_RHO));  // penalty scale (layout.h): the regularisation schedule in its units
   double delta_w = SENS ? 0.0 : STD(ST_FORCE_REG);
   const double dw_last = STD(ST_DW_LAST);
@@ -947,6 +949,7 @@ __device__ __forceinline__ void load_stage1(const StageLds& S, const double p0, 
   s.v[0] = k > 0 ? v0 : p0, s.v[1] = k > 0 ? v1 : p1;
 }
 
+template <bool PI = false>
 __device__ __forceinline__ void d_riccati1(const Consts& K, const Work& W, Ric1Lds& L, const StageLds& S, const int g, const int i, const int b,
                                            const bool valid, const int active_slot, const int max_sweeps) {
   const int N = W.N;
@@ -959,10 +962,10 @@ __device__ __forceinline__ void d_riccati1(const Consts& K, const Work& W, Ric1L
 #define RTOCK(q) if (rprof) { const long long t1 = clock64(); W.DBG[q] += (double)(t1 - rt0); rt0 = t1; }
   bool live, retry;
   double mu;
-  if (!d_head8(K, W, i, b, valid, active_slot, live, retry, mu)) return;
+  if (!d_head8<PI>(K, W, i, b, valid, active_slot, live, retry, mu)) return;
   // ---- backward sweep (whole wave in lock-step; an instance whose Huu fails retries with a larger delta_w,
   //      the others recompute the same numbers)
-  const double r2[2] = {2.0 * K.p.r_du[0], 2.0 * K.p.r_du[1]};
+  const double r2[2] = {2.0 * inst_r_du<PI>(K.p, W, b, 0), 2.0 * inst_r_du<PI>(K.p, W, b, 1)};
   const double psc = pen_scale(STD(ST_RHO));  // penalty scale (layout.h): the regularisation schedule in its units
   double delta_w = STD(ST_FORCE_REG);
   const double dw_last = STD(ST_DW_LAST);
@@ -1252,6 +1255,7 @@ __host__ __device__ constexpr size_t ric1q_lds_bytes(int N) { return sizeof(doub
 // words the stage has just stored to HBM (measured: a stage of k_riccati1q 3500 cycles with __syncthreads()).
 #define WG_SYNC_LDS() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #if !defined(LTOMPC_HOST_HARNESS)
+template <bool PI = false>
 __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1qLds& X, const StageLds& S, const int t, const int b,
                                             const int active_slot, const int max_sweeps) {
   const int N = W.N;
@@ -1269,7 +1273,7 @@ __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1
   int tries = 0;
   bool numerical = false;
   if (w == 0) {
-    const bool go = d_head8(K, W, i, b, g == 0, active_slot, live, retry, mu);
+    const bool go = d_head8<PI>(K, W, i, b, g == 0, active_slot, live, retry, mu);
     psc = pen_scale(STD(ST_RHO));  // penalty scale (layout.h): the regularisation schedule in its units
     dw_last = STD(ST_DW_LAST);
     double delta_w = STD(ST_FORCE_REG);
@@ -1302,7 +1306,7 @@ __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1
   const bool live_w = X.live != 0;  // the instance has a sweep to do (head8 returns true only then: one instance per workgroup)
   mu = X.mu;
   const double up0 = W.uprev[b], up1 = W.uprev[(size_t)W.Bp + b];
-  const double r2[2] = {2.0 * K.p.r_du[0], 2.0 * K.p.r_du[1]};
+  const double r2[2] = {2.0 * inst_r_du<PI>(K.p, W, b, 0), 2.0 * inst_r_du<PI>(K.p, W, b, 1)};
   // roles of wavefront 1: lanes 0 .. 15 = (row, input) pairs, lanes 16 .. 23 = rows
   const int r1 = lane < 16 ? (lane >> 1) : (lane - 16), c1w = lane & 1;
   const int row = w == 0 ? i : (r1 & 7);
@@ -1641,5 +1645,39 @@ __global__ void __launch_bounds__(64) k_riccati1(Consts K, Work W, Launch la, in
   d_riccati1(K, W, L, S, g, i, la.act[blockIdx.x], g == 0, it_index, max_sweeps);
 }
 
+
+// with per-instance vehicle and cost parameters (W.TH)
+__global__ void __launch_bounds__(64) k_riccati8_pi(Consts K, WorkPI W, Launch la, int it_index, int max_sweeps) {
+  __shared__ RicLds L;
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int jj = blockIdx.x * 8 + g;
+  const bool valid = jj < la.nact[0];
+  d_riccati8<false, true>(K, W, L, g, i, la.act[valid ? jj : 0], valid, it_index, max_sweeps);
+}
+__global__ void __launch_bounds__(256) k_riccati1q_pi(Consts K, WorkPI W, Launch la, int it_index, int max_sweeps) {
+#if defined(LTOMPC_HOST_HARNESS)
+  (void)K, (void)W, (void)la, (void)it_index, (void)max_sweeps;  // (never run by the harness)
+#else
+  extern __shared__ double lds1q[];
+  if ((int)blockIdx.x >= la.nact[0]) return;
+  const int N = W.N;
+  StageLds S{lds1q, lds1q + (size_t)N * QP_NF, lds1q + (size_t)N * (QP_NF + 2)};
+  Ric1qLds& X = *reinterpret_cast<Ric1qLds*>(lds1q + (size_t)N * (QP_NF + 24));
+  d_riccati1q<true>(K, W, X, S, threadIdx.x, la.act[blockIdx.x], it_index, max_sweeps);
+#endif
+}
+__global__ void __launch_bounds__(64) k_riccati1_pi(Consts K, WorkPI W, Launch la, int it_index, int max_sweeps) {
+#if defined(LTOMPC_HOST_HARNESS)
+  static double lds1[1];  // (never run by the harness)
+#else
+  extern __shared__ double lds1[];
+#endif
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  if ((int)blockIdx.x >= la.nact[0]) return;
+  const int N = W.N;
+  StageLds S{lds1, lds1 + (size_t)N * QP_NF, lds1 + (size_t)N * (QP_NF + 2)};
+  Ric1Lds& L = *reinterpret_cast<Ric1Lds*>(lds1 + (size_t)N * (QP_NF + 24));
+  d_riccati1<true>(K, W, L, S, g, i, la.act[blockIdx.x], g == 0, it_index, max_sweeps);
+}
 
 }  // namespace ltompc

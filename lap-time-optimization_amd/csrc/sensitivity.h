@@ -34,6 +34,17 @@ __global__ void __launch_bounds__(64) k_sens_eval8(const Consts* __restrict__ Kp
   const bool valid = j < W.B;
   d_eval8(K, W, lds[g], i, k, valid ? j : 0, valid);  // (padding lanes shadow slot 0 read-only)
 }
+// the _pi kernels: with per-instance vehicle and cost parameters (W.TH)
+__global__ void __launch_bounds__(64) k_sens_eval8_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wsp) {
+  const Consts& K = *Kp;
+  const Work& W = *Wsp;
+  __shared__ E8Lds lds[8];
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int G8 = W.Bp >> 3;
+  const int k = blockIdx.x / G8, j = (blockIdx.x % G8) * 8 + g;
+  const bool valid = j < W.B;
+  d_eval8<true>(K, W, lds[g], i, k, valid ? j : 0, valid);  // (padding lanes shadow slot 0 read-only)
+}
 
 template <class BP, bool ELL>
 __global__ void __launch_bounds__(64) k_sens_eval(const Consts* __restrict__ Kp, const Work* __restrict__ Wsp) {
@@ -43,6 +54,15 @@ __global__ void __launch_bounds__(64) k_sens_eval(const Consts* __restrict__ Kp,
   const int b = tid % W.Bp, k = tid / W.Bp;
   if (k >= W.N || b >= W.B) return;
   d_eval<BP, ELL>(K, W, k, b, true);
+}
+template <class BP>
+__global__ void __launch_bounds__(64) k_sens_eval_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wsp) {
+  const Consts& K = *Kp;
+  const Work& W = *Wsp;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = tid % W.Bp, k = tid / W.Bp;
+  if (k >= W.N || b >= W.B) return;
+  d_eval<BP, false, true>(K, W, k, b, true);
 }
 
 // si_solve: the solver's own si planes (read only).  An instance is differentiated when the solver's status (before the
@@ -58,6 +78,18 @@ __global__ void __launch_bounds__(64) k_sens_riccati8(Consts K, Work Ws, const i
   const int status = node0 ? node0 - 1 : si_solve[(size_t)SI_STATUS * Bp + b];
   const bool el = valid && (status == LTOMPC_STATUS_SOLVED || status == LTOMPC_STATUS_ACCEPTABLE) && !si_solve[(size_t)SI_REINIT * Bp + b];
   d_riccati8<true>(K, Ws, L, g, i, b, valid, -1, 1, el, inertia);
+}
+__global__ void __launch_bounds__(64) k_sens_riccati8_pi(Consts K, WorkPI Ws, const int* __restrict__ si_solve, int* __restrict__ inertia) {
+  __shared__ RicLds L;
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int j = blockIdx.x * 8 + g;
+  const bool valid = j < Ws.B;
+  const int b = valid ? j : 0;
+  const size_t Bp = Ws.Bp;
+  const int node0 = si_solve[(size_t)SI_NODE0 * Bp + b];
+  const int status = node0 ? node0 - 1 : si_solve[(size_t)SI_STATUS * Bp + b];
+  const bool el = valid && (status == LTOMPC_STATUS_SOLVED || status == LTOMPC_STATUS_ACCEPTABLE) && !si_solve[(size_t)SI_REINIT * Bp + b];
+  d_riccati8<true, true>(K, Ws, L, g, i, b, valid, -1, 1, el, inertia);
 }
 
 // Forward propagation of the 10 directions.  Wave = 8 instances x 8 lanes; lane (g, i) carries row i of dX_k (10 columns),

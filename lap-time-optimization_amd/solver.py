@@ -33,6 +33,8 @@ class BatchedMPC:
         self._solved = None
         self._fb = None  # (du0_dx0, du0_duprev, ok) of that solve, fetched by the first feedback()
         self._pfb = None  # du0_dtheta of that solve, fetched by the first feedback(theta=...)
+        self._theta_rows = None  # per-instance rows set (set_theta), (B, 16), None: the handle's params, _DEV_ROWS: set_theta_dev
+        self._theta_solved = None  # ... those of the last solve (feedback(theta=...) expands around them)
         self._uprev_next = np.zeros((self.B, NU))
 
     def close(self):
@@ -60,7 +62,10 @@ class BatchedMPC:
         self.iters = np.empty(self.B, dtype=np.int32)
         self._solved = None
         self._fb = self._pfb = None
+        # (rows set from device memory: read back the ones this solve is about to use, for feedback(theta=...))
+        theta_solve = self.instance_theta() if self._theta_rows is _DEV_ROWS else self._theta_rows
         check(lib().ltompc_make_step(self._h, dptr(x0), dptr(u0), iptr(self.status), iptr(self.iters)))
+        self._theta_solved = theta_solve
         if self._uprev_next is not None:
             self._solved = (x0.copy(), self._uprev_next.copy(), u0.copy())
         self._uprev_next = u0.copy()
@@ -79,6 +84,7 @@ class BatchedMPC:
         self._solved = self._uprev_next = None
         self._fb = self._pfb = None
         check(lib().ltompc_make_step_dev(self._h, C.c_void_p(x0_ptr), C.c_void_p(u0_ptr)))
+        self._theta_solved = None  # (feedback() needs a host make_step)
 
     def rollout_dev(self, x_ptr: int, n_ticks: int, n_sub: int = 400, u_log_ptr: int = 0, status_log_ptr: int = 0, iters_log_ptr: int = 0):
         """Closed-loop rollout with free-running instances (ltompc_rollout_dev): n_ticks of make_step + plant step per instance."""
@@ -86,6 +92,7 @@ class BatchedMPC:
         self._fb = self._pfb = None
         check(lib().ltompc_rollout_dev(self._h, C.c_void_p(x_ptr), int(n_ticks), int(n_sub), C.c_void_p(u_log_ptr or None),
                                        C.c_void_p(status_log_ptr or None), C.c_void_p(iters_log_ptr or None)))
+        self._theta_solved = None  # (feedback() needs a host make_step)
         it, ln = C.c_longlong(), C.c_longlong()
         check(lib().ltompc_rollout_info(self._h, C.byref(it), C.byref(ln)))
         return dict(iterations=it.value, launches=ln.value)
@@ -146,23 +153,70 @@ class BatchedMPC:
         p = self.params
         return np.array([getattr(p, n) for n in THETA_NAMES[:-2]] + [p.r_du[0], p.r_du[1]])
 
+    # ---- per-instance vehicle and cost parameters (ltompc_set_instance_params) ----------------------------
+    def set_theta(self, theta):
+        """Per-instance values of the 16 parameters THETA_NAMES, from the next make_step / make_step_dev / rollout_dev / plant_step
+        on (the warm start is kept; sensitivities until then stay those of the last solve).  theta: a (B, 16) array in THETA_NAMES
+        order; or a dict name -> scalar or (B,) array, the other columns from the handle's params; or None: the handle's params
+        again.  Every other field of Params stays the handle's.  Instance b then solves exactly (bit for bit) the NLP of a handle
+        created with row b written into its params."""
+        if theta is None:
+            check(lib().ltompc_set_instance_params(self._h, None))
+            self._theta_rows = None
+            return
+        rows = self._theta_array(theta)
+        check(lib().ltompc_set_instance_params(self._h, dptr(rows)))
+        self._theta_rows = rows
+
+    def set_theta_dev(self, theta_ptr: int):
+        """set_theta from a device array of (B, 16) float64 in THETA_NAMES order (ltompc_set_instance_params_dev): enqueued on
+        the handle's stream, NOT checked.  0 = set_theta(None).  The next host make_step reads the rows back once, so that
+        feedback(theta=...) expands around them."""
+        if not theta_ptr:
+            self.set_theta(None)
+            return
+        check(lib().ltompc_set_instance_params_dev(self._h, C.c_void_p(theta_ptr)))
+        self._theta_rows = _DEV_ROWS
+
+    def _theta_array(self, theta):
+        return _theta_rows(theta, self.B, self.theta())
+
+    def instance_theta(self):
+        """The rows in effect, (B, 16) in THETA_NAMES order (the handle's values in every row when none are set)."""
+        out = np.empty((self.B, NTHETA))
+        check(lib().ltompc_get_instance_params(self._h, dptr(out)))
+        return out
+
     def feedback(self, x, u_prev=None, *, theta=None):
         """Tangential predictor of the last make_step: u0 + du0_dx0 (x - x0_solved) + du0_duprev (u_prev - u_prev_solved), and u0
         where ok is False.  u_prev=None: the u_prev of that solve (no change in those directions).  theta: a dict name -> value
-        of parameters of param_sensitivities() (names in THETA_NAMES) that differ from the handle's; adds du0_dtheta (theta -
-        theta_solved).  theta=None: no change in those directions (and no parameter pass)."""
+        (a scalar or a (B,) array) of parameters of param_sensitivities() (names in THETA_NAMES); adds du0_dtheta (theta -
+        theta_solved), theta_solved = each instance's row of that solve (set_theta / set_theta_dev), else the handle's values.
+        theta=None: no change in those directions (and no parameter pass)."""
         if theta is not None:
             u = self.feedback(x, u_prev)
             if self._pfb is None:  # one host copy per solve, not per call
                 self._pfb = self.param_sensitivities()["du0_dtheta"]
-            d = np.zeros(NTHETA)
-            cur = self.theta()
-            for name, v in theta.items():
+            for name in theta:
                 if name not in THETA_NAMES:
                     raise ValueError(f"feedback: unknown parameter {name!r} (one of {THETA_NAMES})")
+            if self._theta_solved is None and all(np.ndim(v) == 0 for v in theta.values()):  # uniform handle, one value per name
+                d = np.zeros(NTHETA)
+                cur = self.theta()
+                for name, v in theta.items():
+                    j = THETA_NAMES.index(name)
+                    d[j] = float(v) - cur[j]
+                return u + np.einsum("bij,j->bi", self._pfb, d)  # (rows with ok False are 0)
+            # around each instance's solved row; a value per name: a scalar or a (B,) array
+            cur = self._theta_solved if self._theta_solved is not None else np.tile(self.theta(), (self.B, 1))
+            d = np.zeros((self.B, NTHETA))
+            for name, v in theta.items():
                 j = THETA_NAMES.index(name)
-                d[j] = float(v) - cur[j]
-            return u + np.einsum("bij,j->bi", self._pfb, d)  # (rows with ok False are 0)
+                v = np.asarray(v, dtype=np.float64)
+                if v.shape not in ((), (self.B,)):
+                    raise ValueError(f"feedback: {name} must be a scalar or a ({self.B},) array, got shape {v.shape}")
+                d[:, j] = v - cur[:, j]
+            return u + np.einsum("bij,bj->bi", self._pfb, d)
         if self._solved is None:
             raise _lib.LtompcError("feedback: no make_step to expand around (the last solve was not a host make_step, or an "
                                    "initial guess came after it)")
@@ -311,6 +365,35 @@ class BatchedMPC:
         return x0
 
 
+_DEV_ROWS = object()  # BatchedMPC._theta_rows after set_theta_dev: the rows are in device memory only
+
+
+def _theta_rows(theta, B, base):
+    """(B, 16) float64 rows from set_theta's argument; shapes, names and values are checked here, before any call."""
+    if isinstance(theta, dict):
+        rows = np.tile(base, (B, 1))
+        for name, v in theta.items():
+            if name not in THETA_NAMES:
+                raise ValueError(f"set_theta: unknown parameter {name!r} (one of {THETA_NAMES})")
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape not in ((), (B,)):
+                raise ValueError(f"set_theta: {name} must be a scalar or a ({B},) array, got shape {v.shape}")
+            rows[:, THETA_NAMES.index(name)] = v
+    else:
+        rows = np.asarray(theta, dtype=np.float64)
+        if rows.shape != (B, NTHETA):
+            raise ValueError(f"set_theta: theta must be ({B}, {NTHETA}) in THETA_NAMES order, got shape {rows.shape}")
+    rows = np.array(rows, dtype=np.float64, order="C", copy=True)  # (a copy: the caller may reuse its array for the next rows)
+    bad = ~np.isfinite(rows)
+    bad[:, :2] |= ~(rows[:, :2] > 0)
+    bad[:, 11:] |= ~(rows[:, 11:] >= 0)
+    if bad.any():
+        b, j = map(int, np.argwhere(bad)[0])
+        raise ValueError(f"set_theta: row {b}, {THETA_NAMES[j]} = {rows[b, j]!r} (finite values; mass, inertia_z > 0; q_n, q_mu, q_B, "
+                         f"r_du >= 0)")
+    return rows
+
+
 class SplitMPC:
     """The batch as `n_parts` handles of batch / n_parts instances, each on its own HIP stream and driven by its own host thread
     (ctypes releases the GIL during a call).  Instances are independent NLPs, so the parts need not tick together: while one
@@ -417,6 +500,18 @@ class SplitMPC:
     def iterate(self):
         r = [p.iterate() for p in self.parts]
         return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    def set_theta(self, theta):
+        """BatchedMPC.set_theta with the rows split across the parts (a (B, 16) array, a dict of scalars / (B,) arrays, or None)."""
+        if theta is None:
+            self._each(lambda p, lo, hi: p.set_theta(None))
+            return
+        rows = _theta_rows(theta, self.B, self.parts[0].theta())  # (the whole batch checked first: a bad row changes no part)
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.set_theta(rows[lo:hi])
+
+    def instance_theta(self):
+        return np.concatenate([p.instance_theta() for p in self.parts])
 
     def sensitivities(self, trajectory: bool = False):
         """BatchedMPC.sensitivities of every part, stitched in the caller's order."""
