@@ -151,7 +151,9 @@ typedef struct ltompc_options {
   int periodic_tables;    /* 0: tables extrapolate linearly beyond their ends (CasADi's interpolant, the reference) | 1: the track is a
                              closed loop, tables are evaluated at s modulo their span (buckmore: kappa, n_left, n_right
                              agree at both ends, v_ref to 0.2 %), so that the closed loop can run lap after lap; the kink
-                             at the seam is not rounded                                      (0) */
+                             at the seam is not rounded.  One period serves both grids: ltompc_create
+                             refuses tables whose s_arc and s_kappa grids differ in their first knot or in their span by
+                             more than 1e-9 of the span (they would wrap n_left, n_right and v_ref at the wrong place) (0) */
   int max_soc;            /* second-order corrections per iteration (IPOPT's max_soc): when the full step is rejected and
                              does not reduce the constraint violation, the step is re-computed with the constraint
                              residuals of the trial point added (same KKT matrix, new right-hand side: a Riccati sweep

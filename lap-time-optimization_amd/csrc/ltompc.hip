@@ -543,6 +543,18 @@ int ltompc_create(const ltompc_params* params, const ltompc_options* options, co
   for (int i = 1; i < n_table; i++)
     if (!(tables[i] > tables[i - 1]) || !(tables[2 * (size_t)n_table + i] > tables[2 * (size_t)n_table + i - 1]))
       return fail("ltompc_create: table grids must be strictly increasing");
+  if (options->periodic_tables) {
+    // one period for both grids: the look-ups wrap s at g0 + k * span of the grid they read, and a lap is one length
+    const double* ga = tables + 2 * (size_t)n_table;
+    const double span_k = tables[n_table - 1] - tables[0], span_a = ga[n_table - 1] - ga[0];
+    if (!(std::fabs(span_a - span_k) <= 1e-9 * span_k) || !(std::fabs(ga[0] - tables[0]) <= 1e-9 * span_k)) {
+      char msg[320];
+      snprintf(msg, sizeof msg, "ltompc_create: periodic_tables needs both grids to start at the same arc length and to have the same span: "
+               "s_kappa covers [%.17g, %.17g] (span %.17g), s_arc covers [%.17g, %.17g] (span %.17g)",
+               tables[0], tables[n_table - 1], span_k, ga[0], ga[n_table - 1], span_a);
+      return fail(msg);
+    }
+  }
   int ndev = 0;
   HIPCHECK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail("ltompc_create: no such HIP device");

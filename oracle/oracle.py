@@ -78,6 +78,20 @@ class Oracle:
         self.nt = self.tab.shape[1]
         self.p = params or default_params()
         self.o = options or default_options()
+        self._check_period()
+
+    def _check_period(self):
+        """options.periodic_tables wraps both grids with the span of s_kappa (as the device library does): tables whose grids
+        differ in first knot or span have no such period, and ltompc_create refuses them.  So does the oracle, in the
+        constructor and (the options are a mutable attribute) before every solve and plant step."""
+        if not self.o.periodic_tables:
+            return
+        gk, ga = self.tab[0], self.tab[2]
+        gk, ga = [float(v) for v in gk[[0, -1]]], [float(v) for v in ga[[0, -1]]]
+        span_k, span_a = gk[-1] - gk[0], ga[-1] - ga[0]
+        if not (abs(span_a - span_k) <= 1e-9 * span_k and abs(ga[0] - gk[0]) <= 1e-9 * span_k):
+            raise ValueError(f"Oracle: periodic_tables needs both grids to start at the same arc length and to have the same span: "
+                             f"s_kappa covers [{gk[0]!r}, {gk[-1]!r}] (span {span_k!r}), s_arc covers [{ga[0]!r}, {ga[-1]!r}] (span {span_a!r})")
 
     # ---- model pieces -------------------------------------------------------------
     def rhs(self, x, u):
@@ -118,6 +132,7 @@ class Oracle:
         return a, F
 
     def plant_step(self, x, u, dt=None, n_sub=400):
+        self._check_period()
         x = np.ascontiguousarray(np.atleast_2d(x), float); u = np.ascontiguousarray(np.atleast_2d(u), float)
         xn = np.zeros_like(x)
         lib().oracle_plant_step(C.byref(self.p), _p(self.tab), self.nt, _p(x), _p(u), x.shape[0],
@@ -133,6 +148,7 @@ class Oracle:
         sticky: int32 array (B,), in/out: option resto_sticky (ticks for which an instance starts in elastic mode); the
         caller keeps it between ticks (the device library keeps it in the handle).
         Returns dict(u0, X, C, U, L1, L2, status, iters, kkt, obj, mu, n_reg, n_lsfail, n_soc, n_resto, viol, g0, n_fallback)."""
+        self._check_period()
         x0 = np.ascontiguousarray(np.atleast_2d(x0), float)
         B = x0.shape[0]
         uprev = np.zeros((B, 2)) if uprev is None else np.ascontiguousarray(np.atleast_2d(uprev), float)

@@ -5,7 +5,8 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DLTOMPC_HOST_HARNESS -I<csrc> -I<harness> ...
 // Reads a problem from a text file (tables, x0 batch, horizon, options), runs the interior-point iterations with the same
 // launch sequence as ltompc_make_step_dev (identity instance list, no re-packing), prints status / iterations / u0 per
-// instance.  tests/test_host_harness.py compares that with the oracle.  NOT a product path and not an oracle: nothing in
+// instance.  tests/test_host_harness.py compares that with the oracle.  With model_eps=<eps> it evaluates the model functions
+// and their derivatives at given points instead (tests/test_synthetic_tracks.py).  NOT a product path and not an oracle: nothing in
 // the package or in bench.py uses it.
 #include "layout.h"
 #include "linearise.h"
@@ -105,8 +106,11 @@ int main(int argc, char** argv) {
   memset(&K, 0, sizeof K);
   default_params(&K.p), default_options(&K.o);
   K.o.soft_rho = soft_rho;
-  for (int a = 2; a < argc; a++)
+  double model_eps = -1.0;  // model_eps=<eps>: model mode (below) instead of solves
+  for (int a = 2; a < argc; a++) {
+    if (!strncmp(argv[a], "model_eps=", 10)) { model_eps = atof(argv[a] + 10); continue; }
     if (!set_option(&K.o, argv[a])) return fprintf(stderr, "harness: unknown option %s\n", argv[a]), 2;
+  }
   K.p.ell_penalty = ell[0], K.p.ell_rho = ell[1], K.p.ell_D_f = ell[2], K.p.ell_D_r = ell[3];
   build_bounds(K.p, K.bd);
   const int ni = K.bd.ni, Bp = (B + 63) / 64 * 64;
@@ -117,6 +121,26 @@ int main(int argc, char** argv) {
   T.g0_kappa = tab[0], T.inv_kappa = (double)(nt - 1) / (tab[nt - 1] - tab[0]);
   T.g0_arc = tab[2 * (size_t)nt], T.inv_arc = (double)(nt - 1) / (tab[3 * (size_t)nt - 1] - tab[2 * (size_t)nt]);
   T.period = 0.0;
+  if (model_eps >= 0.0) {
+    // Model mode: the batch is B / 2 states followed by B / 2 rows of multipliers.  k_test_model (the kernel behind
+    // ltompc_test_model) at those points with smoothing length model_eps, every output in a NaN-poisoned buffer of its exact
+    // size; one line per point: f[8] J[64] H[64] cval[2] cgrad[16] cH[128] gval[3] ggrad[24] gH[192].
+    const int n = B / 2;
+    const size_t sz[9] = {8, 64, 64, 2, 16, 128, 3, 24, 192};
+    double* out[9];
+    for (int i = 0; i < 9; i++) out[i] = poisoned(sz[i] * n);
+    double *xs = (double*)malloc(sizeof(double) * 8 * n), *ls = (double*)malloc(sizeof(double) * 8 * n);
+    memcpy(xs, x0.data(), sizeof(double) * 8 * n), memcpy(ls, x0.data() + (size_t)8 * n, sizeof(double) * 8 * n);
+    const Consts Kc = K;
+    grid64(n, [&] { k_test_model(Kc, n, model_eps, xs, ls, out[0], out[1], out[2], out[3], out[4], out[5], out[6], out[7], out[8]); });
+    printf("tick 0\n");
+    for (int t = 0; t < n; t++) {
+      for (int i = 0; i < 9; i++)
+        for (size_t j = 0; j < sz[i]; j++) printf("%.17g ", out[i][t * sz[i] + j]);
+      printf("\n");
+    }
+    return 0;
+  }
   Work W;
   memset(&W, 0, sizeof W);
   W.N = N, W.B = B, W.Bp = Bp;
