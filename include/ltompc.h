@@ -367,6 +367,43 @@ int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev);
 int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok);
 int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev);
 
+/* Adjoint sensitivities of the last solve: the gradient of a scalar loss L(X, U) of the predicted trajectory
+ * w.r.t. p = (x0[0..7], u_prev[0..1]) and theta (the LTOMPC_NTHETA = 16 columns above), from its cotangents gX = dL/dX and
+ * gU = dL/dU, without forming a Jacobian.  For instance b:
+ *     grad_p[j]     = sum_{k,i} gX[k,i] dX_dp[k,i,j]  + sum_{k,c} gU[k,c] dU_dp[k,c,j],     j < 10
+ *     grad_theta[j] = sum_{k,i} gX[k,i] dX_dth[k,i,j] + sum_{k,c} gU[k,c] dU_dth[k,c,j],    j < 16
+ * with dX_dp, dU_dp, dX_dth, dU_dth exactly the outputs of ltompc_get_sensitivities and ltompc_get_param_sensitivities (same
+ * definition, same instances).  Block 0 of dX_dp is [I_8 | 0]: gX[0] lands in grad_p[0..7] as it is; block 0 of dX_dth is 0.
+ *   ok[b] equals ltompc_get_sensitivities' ok[b] bit for bit; every output of an instance with ok[b] = 0 is exactly 0.
+ * The KKT matrix is symmetric, so this is ONE more solve on the delta_w = 0 factorisation with the cotangent as right-hand
+ * side (a backward and a forward recursion of vectors), contracted with the condensed right-hand sides of the 16 columns.
+ *
+ * Inputs, in the caller's instance order:
+ *   gX  batch x (N+1) x 8;   gU  batch x N x 2.   Either may be NULL (= zeros); both NULL is a usage error.
+ * Outputs, in the caller's instance order, any may be NULL:
+ *   grad_p  batch x 10 (x0[0..7], u_prev[0..1]);   grad_theta  batch x 16;   ok  batch ints.
+ *   grad_theta = NULL skips the parameter part of the pass (no right-hand sides are condensed, no forward recursion).
+ * ltompc_get_adjoint: host pointers.  A non-finite cotangent is a usage error that names the instance.
+ * ltompc_adjoint_dev: device pointers, enqueues only, on the handle's stream.  The cotangents are NOT checked.  The first
+ *   request on a handle allocates the pass's buffers and synchronises once (as for ltompc_sensitivities_dev; the first one
+ *   with grad_theta allocates the parameter part's the same way).
+ *
+ * The result refers to the last solve of each instance; before any solve and after set_initial_guess(_dev) a call is a usage
+ * error.  grad_theta has the limits of ltompc_get_param_sensitivities: a handle with ell_penalty > 0 or ptv != 0, and a call
+ * after rollout_dev, are usage errors; grad_p alone is available there.  With per-instance rows the gradients are those at the
+ * rows the solve used.  The re-linearisation, the factorisation and the condensed right-hand sides are shared with the two
+ * forward passes (whichever runs first for a solve makes them); nothing is kept per cotangent.  The pass writes buffers of its
+ * own only: every later make_step, rollout or forward pass gives the bits it would have given without it. */
+int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, double* grad_p, double* grad_theta, int* ok);
+int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_p_dev, double* grad_theta_dev,
+                       int* ok_dev);
+
+/* ltompc_get_prediction into device memory: X_dev (row-major batch x (N+1) x 8) and U_dev (batch x N x 2) in the caller's
+ * instance order, either may be NULL.  Enqueues only, on the handle's stream.  Unlike ltompc_get_prediction it reads the
+ * instances where they are and does not restore the caller's order inside the handle: a device-side loop (a loss on the
+ * prediction, ltompc_adjoint_dev, the next make_step_dev) never pays for un-packing. */
+int ltompc_get_prediction_dev(ltompc_handle h, double* X_dev, double* U_dev);
+
 /* Per-instance vehicle and cost parameters.  Instance b may have its own row theta_b: the LTOMPC_NTHETA = 16
  * values of ltompc_get_param_sensitivities' columns, in that order and in natural units.  Every other field of ltompc_params
  * stays the handle's.  Instance b's NLP, plant step and sensitivities are then bit for bit those of a handle created with

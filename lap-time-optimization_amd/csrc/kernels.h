@@ -24,6 +24,9 @@
 //                 (ltompc_get_sensitivities): re-linearisation, head-less Riccati sweep at delta_w = 0, forward propagation
 //   param_sensitivity.h k_psens_*: the same w.r.t. the vehicle and cost parameters (ltompc_get_param_sensitivities): condensed
 //                 right-hand sides of the 16 columns, their backward recursion on the stored factorisation, forward pass
+//   adjoint.h     k_adj_sweep: the gradient of a loss of the predicted trajectory w.r.t. (x0, u_prev, theta) from its cotangents
+//                 (ltompc_get_adjoint): one backward / forward recursion of vectors on the same factorisation, contracted with
+//                 k_psens_cond's planes; k_prediction_dev: the prediction as device arrays in the caller's order
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
@@ -38,3 +41,4 @@
 #include "rollout.h"
 #include "sensitivity.h"
 #include "param_sensitivity.h"
+#include "adjoint.h"

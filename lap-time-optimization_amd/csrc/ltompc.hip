@@ -104,6 +104,12 @@ struct ltompc_solver {
   double* d_psens_uprev = nullptr;
   bool psens_uprev = false;
   double *d_psens_pv = nullptr, *d_psens_kf = nullptr, *d_psens_du0 = nullptr, *d_psens_dX = nullptr, *d_psens_dU = nullptr;
+  // d_psens_pv holds k_psens_cond's planes of the last solve at the instances' current slots (both passes that read them run
+  // the kernel only when it does not).  Cleared whenever the factorisation is made again: a new solve, or the instances moved.
+  bool psens_pv_valid = false;
+  // adjoint pass (adjoint.h, ltompc_get_adjoint): buffers of its own, allocated on the first request; nothing is cached per
+  // cotangent.  d_adj_gX / d_adj_gU: staging of the host form's cotangents.
+  double *d_adj_aj = nullptr, *d_adj_gp = nullptr, *d_adj_gth = nullptr, *d_adj_gX = nullptr, *d_adj_gU = nullptr;
   Work Ws{};                // W with QP, RC, RS, LS -> the pass's buffers, si -> zeros
   Work* d_Ws = nullptr;
   int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
@@ -330,6 +336,7 @@ int sync_pi_work(ltompc_solver* h);
 // again only when the instances have moved since (same blocks, same bits, at their new slots).
 void sens_factorise(ltompc_solver* h) {
   if (h->sens_fact) return;
+  h->psens_pv_valid = false;  // (a new solve, or the instances have moved: k_psens_cond's planes are as stale as the blocks)
   const int N = h->N, Bp = h->Bp;
   const bool ell = h->K.bd.nel > 0;  // the evaluation kernels the solve used (launch_iteration)
   if (h->pi_solve) {  // (at each instance's rows of that solve, TH)
@@ -392,9 +399,8 @@ int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
   return 0;
 }
 
-// The parameter-sensitivity pass of the last solve (param_sensitivity.h): ok (and du0 / margin) of the pass above, whose
-// factorisation it shares, then the condensed right-hand sides of the 16 columns and their recursion.  Cached like the above.
-int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
+// What both passes over theta need: a problem that theta covers, a solve to differentiate whose u_prev was kept, the PV buffers.
+int psens_prepare(ltompc_solver* h, const char* who) {
   if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
   if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
   if (sens_compute(h, false, who)) return -1;  // (the usage error before a solve comes from here)
@@ -406,28 +412,72 @@ int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
     rc |= h->dalloc(&h->d_psens_du0, (size_t)2 * PS_NT * B);
     if (rc) return -1;
   }
+  return 0;
+}
+
+// The factorisation and k_psens_cond's PV planes at the instances' current slots, each only when not there already.
+void psens_condense(ltompc_solver* h) {
+  sens_factorise(h);
+  if (h->psens_pv_valid) return;
+  const int N = h->N, Bp = h->Bp;
+  if (h->pi_solve)
+    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond_pi<BoundsRef> : k_psens_cond_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                       (const Consts*)h->d_K, (const WorkPI*)h->d_Wpi, h->d_psens_pv);
+  else
+    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                       (const Consts*)h->d_K, (const Work*)h->d_W, h->d_psens_pv);
+  h->psens_pv_valid = true;
+}
+
+// The parameter-sensitivity pass of the last solve (param_sensitivity.h): ok (and du0 / margin) of the pass above, whose
+// factorisation it shares, then the condensed right-hand sides of the 16 columns and their recursion.  Cached like the above.
+int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
+  if (psens_prepare(h, who)) return -1;
+  const int B = h->B, N = h->N, Bp = h->Bp;
   if (traj && !h->d_psens_dX) {
     int rc = h->dalloc(&h->d_psens_dX, (size_t)(N + 1) * 8 * PS_NT * B);
     rc |= h->dalloc(&h->d_psens_dU, (size_t)N * 2 * PS_NT * B);
     if (rc) return -1;
   }
   if (h->psens_state == 0 || (traj && h->psens_state == 1)) {
-    sens_factorise(h);
+    psens_condense(h);
     if (h->pi_solve) {
-      hipLaunchKernelGGL(h->ref_eval ? k_psens_cond_pi<BoundsRef> : k_psens_cond_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
-                         (const Consts*)h->d_K, (const WorkPI*)h->d_Wpi, h->d_psens_pv);
       hipLaunchKernelGGL(k_psens_sweep_pi, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Wspi, (const double*)h->d_psens_uprev,
                          (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
                          traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
     } else {
-      hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
-                         (const Consts*)h->d_K, (const Work*)h->d_W, h->d_psens_pv);
       hipLaunchKernelGGL(k_psens_sweep, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1],
                          (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
                          traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
     }
     h->psens_state = traj ? 2 : 1;
   }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The adjoint pass of the last solve (adjoint.h) for one cotangent (device pointers, caller's order; either may be null), into
+// d_adj_gp and, with theta, d_adj_gth: the factorisation and the PV planes when not there, then one sweep.  Once its buffers
+// exist it only enqueues.
+int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, const bool theta, const char* who) {
+  if (!gX_dev && !gU_dev) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  if (theta ? psens_prepare(h, who) : sens_compute(h, false, who)) return -1;
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!h->d_adj_gp) {
+    int rc = h->dalloc(&h->d_adj_gp, (size_t)ADJ_NP * B);
+    rc |= h->dalloc(&h->d_adj_gth, (size_t)PS_NT * B);
+    if (rc) return -1;
+  }
+  if (theta && !h->d_adj_aj && h->dalloc(&h->d_adj_aj, (size_t)AJ_NF * N * Bp, true)) return -1;
+  if (theta) psens_condense(h);
+  else sens_factorise(h);
+  double* const gth = theta ? h->d_adj_gth : nullptr;
+  if (h->pi_solve)
+    hipLaunchKernelGGL(k_adj_sweep_pi, dim3(Bp / 8), dim3(64), 0, h->stream, h->Wspi, (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv,
+                       (const int*)h->d_sens_ok, gX_dev, gU_dev, h->d_adj_aj, h->d_adj_gp, gth);
+  else
+    hipLaunchKernelGGL(k_adj_sweep, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1], (const double*)h->d_psens_uprev,
+                       (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, gX_dev, gU_dev, h->d_adj_aj, h->d_adj_gp, gth);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1111,6 +1161,51 @@ int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok
   const size_t B = h->B;
   if (du0_dth_dev) HIPCHECK(hipMemcpyAsync(du0_dth_dev, h->d_psens_du0, sizeof(double) * 2 * PS_NT * B, hipMemcpyDeviceToDevice, h->stream));
   if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_p_dev, double* grad_theta_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (adj_compute(h, gX_dev, gU_dev, grad_theta_dev != nullptr, "ltompc_adjoint_dev")) return -1;
+  const size_t B = h->B;
+  if (grad_p_dev) HIPCHECK(hipMemcpyAsync(grad_p_dev, h->d_adj_gp, sizeof(double) * ADJ_NP * B, hipMemcpyDeviceToDevice, h->stream));
+  if (grad_theta_dev) HIPCHECK(hipMemcpyAsync(grad_theta_dev, h->d_adj_gth, sizeof(double) * PS_NT * B, hipMemcpyDeviceToDevice, h->stream));
+  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, double* grad_p, double* grad_theta, int* ok) {
+  const char* who = "ltompc_get_adjoint";
+  if (!h) return fail("null handle");
+  if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  const size_t B = h->B, N = h->N;
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; gX && e < (N + 1) * 8; e++) fin = fin && std::isfinite(gX[b * (N + 1) * 8 + e]);
+    for (size_t e = 0; gU && e < N * 2; e++) fin = fin && std::isfinite(gU[b * N * 2 + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite cotangent of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  if (gX && !h->d_adj_gX && h->dalloc(&h->d_adj_gX, (N + 1) * 8 * B)) return -1;
+  if (gU && !h->d_adj_gU && h->dalloc(&h->d_adj_gU, N * 2 * B)) return -1;
+  if (gX) HIPCHECK(hipMemcpyAsync(h->d_adj_gX, gX, sizeof(double) * (N + 1) * 8 * B, hipMemcpyHostToDevice, h->stream));
+  if (gU) HIPCHECK(hipMemcpyAsync(h->d_adj_gU, gU, sizeof(double) * N * 2 * B, hipMemcpyHostToDevice, h->stream));
+  if (adj_compute(h, gX ? h->d_adj_gX : nullptr, gU ? h->d_adj_gU : nullptr, grad_theta != nullptr, who)) return -1;
+  if (grad_p) HIPCHECK(hipMemcpyAsync(grad_p, h->d_adj_gp, sizeof(double) * ADJ_NP * B, hipMemcpyDeviceToHost, h->stream));
+  if (grad_theta) HIPCHECK(hipMemcpyAsync(grad_theta, h->d_adj_gth, sizeof(double) * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
+  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_get_prediction_dev(ltompc_handle h, double* X_dev, double* U_dev) {
+  if (!h) return fail("null handle");
+  if (!X_dev && !U_dev) return 0;
+  HIPCHECK(hipSetDevice(h->device));
+  const size_t nthreads = (size_t)(h->N + 1) * h->Bp;
+  hipLaunchKernelGGL(k_prediction_dev, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, h->stream, h->W, X_dev, U_dev);
+  HIPCHECK(hipGetLastError());
   return 0;
 }
 

@@ -148,6 +148,45 @@ class BatchedMPC:
         handle's stream."""
         check(lib().ltompc_param_sensitivities_dev(self._h, C.c_void_p(du0_dth_ptr or None), C.c_void_p(ok_ptr or None)))
 
+    # ---- adjoint sensitivities: the gradient of a loss of the prediction (ltompc_get_adjoint, DESIGN.md §11) -----------
+    def adjoint(self, gX=None, gU=None, theta: bool = True):
+        """Gradient of a scalar loss L(X, U) of the last solve's predicted trajectory w.r.t. (x0, u_prev) and, with theta=True,
+        the 16 parameters THETA_NAMES, from its cotangents gX = dL/dX (B,N+1,8) and gU = dL/dU (B,N,2) (None: zeros; not both):
+        the contraction of sensitivities(trajectory=True) and param_sensitivities(trajectory=True) with (gX, gU), in one sweep
+        and without the Jacobians.
+
+        Returns grad_x0 (B,8), grad_uprev (B,2), grad_theta (B,16, only with theta=True), names, ok (B,) bool (the same as
+        sensitivities()' ok).  Where ok is False every output of the instance is 0."""
+        B, N = self.B, self.N
+        if gX is not None:
+            gX = np.ascontiguousarray(gX, dtype=np.float64)
+            if gX.shape != (B, N + 1, NX):
+                raise ValueError(f"adjoint: gX must have shape {(B, N + 1, NX)}, got {gX.shape}")
+        if gU is not None:
+            gU = np.ascontiguousarray(gU, dtype=np.float64)
+            if gU.shape != (B, N, NU):
+                raise ValueError(f"adjoint: gU must have shape {(B, N, NU)}, got {gU.shape}")
+        gp, ok = np.empty((B, 10)), np.empty(B, dtype=np.int32)
+        gth = np.empty((B, NTHETA)) if theta else None
+        check(lib().ltompc_get_adjoint(self._h, dptr(gX) if gX is not None else None, dptr(gU) if gU is not None else None,
+                                       dptr(gp), dptr(gth) if theta else None, iptr(ok)))
+        out = dict(grad_x0=gp[:, :NX].copy(), grad_uprev=gp[:, NX:].copy(), names=THETA_NAMES, ok=ok != 0)
+        if theta:
+            out["grad_theta"] = gth
+        return out
+
+    def adjoint_dev(self, gX_ptr: int, gU_ptr: int, grad_p_ptr: int = 0, grad_theta_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue the adjoint pass of the last solve on the handle's stream: cotangents from device arrays (B,N+1,8) / (B,N,2)
+        of doubles (0: zeros; not both, NOT checked for finiteness), results into device buffers (B,10) (x0[0..7], u_prev[0..1])
+        / (B,16) doubles / (B,) int32; grad_theta_ptr = 0 skips the parameter part of the pass."""
+        check(lib().ltompc_adjoint_dev(self._h, C.c_void_p(gX_ptr or None), C.c_void_p(gU_ptr or None), C.c_void_p(grad_p_ptr or None),
+                                       C.c_void_p(grad_theta_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    def prediction_dev(self, X_ptr: int = 0, U_ptr: int = 0):
+        """Enqueue a copy of the last solve's prediction into device arrays (B,N+1,8) / (B,N,2) of doubles in the caller's
+        order, on the handle's stream (prediction() without the host; the instances stay packed as they are)."""
+        check(lib().ltompc_get_prediction_dev(self._h, C.c_void_p(X_ptr or None), C.c_void_p(U_ptr or None)))
+
     def theta(self):
         """The handle's values of the 16 parameters of param_sensitivities(), in THETA_NAMES order."""
         p = self.params
@@ -533,3 +572,26 @@ class SplitMPC:
         stream."""
         for p, (lo, hi) in zip(self.parts, self.bounds):
             p.param_sensitivities_dev(du0_dth_ptr + 8 * NU * NTHETA * lo if du0_dth_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def adjoint(self, gX=None, gU=None, theta: bool = True):
+        """BatchedMPC.adjoint of every part with its rows of the cotangents, stitched in the caller's order."""
+        gX = None if gX is None else np.asarray(gX, dtype=np.float64)
+        gU = None if gU is None else np.asarray(gU, dtype=np.float64)
+        r = [p.adjoint(None if gX is None else gX[lo:hi], None if gU is None else gU[lo:hi], theta)
+             for p, (lo, hi) in zip(self.parts, self.bounds)]
+        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+
+    def adjoint_dev(self, gX_ptr: int, gU_ptr: int, grad_p_ptr: int = 0, grad_theta_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.adjoint_dev of every part on its rows of (B,N+1,8) / (B,N,2) cotangents into its rows of (B,10) / (B,16)
+        doubles / (B,) int32, each on its part's stream."""
+        N = self.N
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.adjoint_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0,
+                          grad_p_ptr + 8 * 10 * lo if grad_p_ptr else 0, grad_theta_ptr + 8 * NTHETA * lo if grad_theta_ptr else 0,
+                          ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def prediction_dev(self, X_ptr: int = 0, U_ptr: int = 0):
+        """BatchedMPC.prediction_dev of every part into its rows of (B,N+1,8) / (B,N,2) doubles, each on its part's stream."""
+        N = self.N
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.prediction_dev(X_ptr + 8 * (N + 1) * NX * lo if X_ptr else 0, U_ptr + 8 * N * NU * lo if U_ptr else 0)
