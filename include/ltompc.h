@@ -31,6 +31,7 @@ extern "C" {
 #define LTOMPC_NO_BOUND 1.0e30 /* |bound| >= this means "not set" (controller.py:78 `not_set`) */
 #define LTOMPC_TABLE_ROWS 6    /* s_kappa, kappa, s_arc, n_left, n_right, v_ref */
 #define LTOMPC_NTHETA 16       /* columns of ltompc_get_param_sensitivities (order given there)   */
+#define LTOMPC_NLOOP 24        /* columns of ltompc_get_loop_sensitivities: x_init[0..7], theta[0..15] */
 
 /* per-instance solver status written by make_step */
 #define LTOMPC_STATUS_SOLVED 0          /* scaled KKT error <= tol                                */
@@ -424,6 +425,52 @@ int ltompc_get_prediction_dev(ltompc_handle h, double* X_dev, double* U_dev);
 int ltompc_set_instance_params(ltompc_handle h, const double* theta);
 int ltompc_set_instance_params_dev(ltompc_handle h, const double* theta_dev);
 int ltompc_get_instance_params(ltompc_handle h, double* theta);
+
+/* Sensitivities of the plant step: the derivative of the discrete map that ltompc_plant_step computes - the
+ * tangent of the same 4 x n_sub RK4 stage evaluations, the curvature table as the plant takes it (exact, slope of the current
+ * interval) - at (x, u), with the rows in effect when per-instance rows are set (as ltompc_plant_step).
+ *   x_next      batch x 8: the plant step itself, bit for bit ltompc_plant_step's;
+ *   dxn_dx      batch x 8 x 8;     dxn_du  batch x 8 x 2;
+ *   dxn_dtheta  batch x 8 x 16, the columns of ltompc_get_param_sensitivities in natural units: the 11 dynamics columns (rows
+ *               vx, vy, r of the model), the five cost columns exactly 0.
+ * Outputs may be NULL.  A handle with ptv != 0 refuses dxn_dtheta (usage error); dxn_dx and dxn_du are available there.
+ * ltompc_plant_sensitivities: host pointers.  ltompc_plant_sensitivities_dev: device pointers, enqueues only, on the handle's
+ * stream; the first request on a handle allocates the pass's buffers and synchronises once.  n_sub < 1 is a usage error. */
+int ltompc_plant_sensitivities(ltompc_handle h, const double* x, const double* u, int n_sub, double* x_next, double* dxn_dx,
+                               double* dxn_du, double* dxn_dtheta);
+int ltompc_plant_sensitivities_dev(ltompc_handle h, const double* x_dev, const double* u_dev, int n_sub, double* x_next_dev,
+                                   double* dxn_dx_dev, double* dxn_du_dev, double* dxn_dtheta_dev);
+
+/* Closed-loop sensitivities: the derivative of where the loop  u0_t = make_step(x_t); x_{t+1} = plant(x_t, u0_t)
+ * actually is after T ticks, w.r.t. q = (x_init[0..7], theta[0..15]): LTOMPC_NLOOP = 24 columns, theta in the order and units of
+ * ltompc_get_param_sensitivities.  Per instance the handle keeps Sx = dx_t/dq (8 x 24) and Du = du_{t-1}/dq (2 x 24) on the device.
+ *   ltompc_loop_begin(mode): Sx = [I_8 | 0], Du = 0, ok = 1, ticks = 0.  mode is a bit mask, 1 .. 3: bit 1 - theta enters the
+ *     controller, bit 2 - theta enters the plant (1: tune the controller's model against a fixed car, 2: the car changes under a
+ *     fixed controller, 3: both).  A handle with ell_penalty > 0 or ptv != 0 is a usage error (ltompc_get_param_sensitivities'
+ *     limits).  The first call allocates the buffers and synchronises once; a handle that never asks pays nothing.
+ *   ltompc_loop_tick_dev(x_dev, u0_dev, n_sub, x_next_dev): after make_step(_dev) at x_dev that returned u0_dev.  With K0, Kv0
+ *     (ltompc_sensitivities_dev) and Tth (ltompc_param_sensitivities_dev) of that solve and Phi_x, Phi_u, Phi_th of the plant step
+ *     at (x_t, u0_t):
+ *         Du <- K0 Sx + Kv0 Du + [mode & 1] (Tth into the theta columns)
+ *         Sx <- Phi_x Sx + Phi_u Du + [mode & 2] (Phi_th into the theta columns)
+ *     and x_next_dev = the plant step (bit for bit ltompc_plant_step_dev's).  Enqueues only, on the handle's stream.  An instance
+ *     whose solve has ok = 0 (ltompc_get_sensitivities') leaves the loop: its loop ok becomes 0, its Sx and Du are exactly 0 from
+ *     that tick on, its tick counter stops; x_next is still the plant's.  Usage errors: no ltompc_loop_begin; no new make_step
+ *     since the last tick; the last solve discarded by set_initial_guess or made by rollout_dev (it does not keep u_prev);
+ *     n_sub < 1; a null argument.  The plant step uses the rows in effect (ltompc_plant_step's rule), the solve's derivatives the
+ *     rows the solve used.
+ *   ltompc_loop_tick: the same with host pointers (x, u0: in, x_next: out), synchronous.
+ *   ltompc_get_loop_sensitivities: host outputs, any may be NULL: dx_dq batch x 8 x 24, du_dq batch x 2 x 24, ok and ticks batch ints
+ *     (ticks: the ticks accumulated while ok).  ltompc_loop_sensitivities_dev: device pointers (dx_dq, du_dq, ok), enqueues only.
+ *   ltompc_loop_end: ends the loop (a tick is a usage error until the next ltompc_loop_begin); the last values stay readable.
+ * The passes write buffers of their own only: every later make_step, rollout, sensitivity or adjoint call gives the bits it would
+ * have given without them. */
+int ltompc_loop_begin(ltompc_handle h, int mode);
+int ltompc_loop_tick_dev(ltompc_handle h, const double* x_dev, const double* u0_dev, int n_sub, double* x_next_dev);
+int ltompc_loop_tick(ltompc_handle h, const double* x, const double* u0, int n_sub, double* x_next);
+int ltompc_get_loop_sensitivities(ltompc_handle h, double* dx_dq, double* du_dq, int* ok, int* ticks);
+int ltompc_loop_sensitivities_dev(ltompc_handle h, double* dx_dq_dev, double* du_dq_dev, int* ok_dev);
+int ltompc_loop_end(ltompc_handle h);
 
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:

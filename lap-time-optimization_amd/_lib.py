@@ -13,6 +13,9 @@ NX, NU = 8, 2
 THETA_NAMES = ("mass", "inertia_z", "B_f", "C_f", "D_f", "B_r", "C_r", "D_r", "C_m", "Cr_0", "Cr_2", "q_n", "q_mu", "q_B",
                "r_du[0]", "r_du[1]")
 NTHETA = len(THETA_NAMES)
+# columns of ltompc_get_loop_sensitivities (LTOMPC_NLOOP): the initial state, then theta
+LOOP_NAMES = tuple(f"x_init[{i}]" for i in range(8)) + THETA_NAMES
+NLOOP = len(LOOP_NAMES)
 NO_BOUND = 1.0e30
 STATUS_NAMES = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "numerical", 4: "stalled", 5: "infeasible"}
 
@@ -74,6 +77,14 @@ def lib() -> C.CDLL:
         L.ltompc_set_instance_params.argtypes = [C.c_void_p, _dp]
         L.ltompc_set_instance_params_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_get_instance_params.argtypes = [C.c_void_p, _dp]
+        L.ltompc_plant_sensitivities.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]
+        L.ltompc_plant_sensitivities_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_loop_begin.argtypes = [C.c_void_p, C.c_int]
+        L.ltompc_loop_tick_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ltompc_loop_tick.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp]
+        L.ltompc_get_loop_sensitivities.argtypes = [C.c_void_p, _dp, _dp, _ip, _ip]
+        L.ltompc_loop_sensitivities_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_loop_end.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 

@@ -110,6 +110,13 @@ struct ltompc_solver {
   // adjoint pass (adjoint.h, ltompc_get_adjoint): buffers of its own, allocated on the first request; nothing is cached per
   // cotangent.  d_adj_gX / d_adj_gU: staging of the host form's cotangents.
   double *d_adj_aj = nullptr, *d_adj_gp = nullptr, *d_adj_gth = nullptr, *d_adj_gX = nullptr, *d_adj_gU = nullptr;
+  // plant-step and closed-loop sensitivities (plant_sensitivity.h): buffers of their own.  d_psn_planes: k_plant_sens'
+  // [PSN_NF][Bp] planes (first request of either kind), d_psn_rm: row-major staging of the host forms; the loop's Sx, Du, ok and
+  // ticks (first loop_begin).  loop_fresh: a make_step has run since the last tick.
+  double *d_psn_planes = nullptr, *d_psn_rm = nullptr, *d_loop_Sx = nullptr, *d_loop_Du = nullptr;
+  int *d_loop_ok = nullptr, *d_loop_ticks = nullptr;
+  int loop_mode = 0;
+  bool loop_active = false, loop_fresh = false;
   Work Ws{};                // W with QP, RC, RS, LS -> the pass's buffers, si -> zeros
   Work* d_Ws = nullptr;
   int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
@@ -528,6 +535,46 @@ int commit_theta(ltompc_solver* h) {
   return 0;
 }
 
+// k_plant_sens' planes and the row-major staging of the host forms and, with `loop`, the closed loop's state: each on the first
+// request, with one synchronisation.
+int psn_prepare(ltompc_solver* h, const bool loop) {
+  int rc = 0;
+  bool fresh = false;
+  if (!h->d_psn_planes) {
+    rc |= h->dalloc(&h->d_psn_planes, (size_t)PSN_NF * h->Bp, true), rc |= h->dalloc(&h->d_psn_rm, (size_t)PSN_NF * h->B);
+    fresh = true;
+  }
+  if (loop && !h->d_loop_Sx) {
+    rc |= h->dalloc(&h->d_loop_Sx, (size_t)8 * LOOP_NQ * h->Bp), rc |= h->dalloc(&h->d_loop_Du, (size_t)2 * LOOP_NQ * h->Bp);
+    rc |= h->dalloc(&h->d_loop_ok, h->Bp), rc |= h->dalloc(&h->d_loop_ticks, h->Bp);
+    fresh = true;
+  }
+  if (rc) return -1;
+  if (fresh) HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// The plant-step sensitivities at (x_dev, u_dev) into the planes, with the rows in effect (those set last, as the plant step).
+int psn_launch(ltompc_solver* h, const double* x_dev, const double* u_dev, const int n_sub, const bool theta) {
+  const dim3 grid((h->B + 7) / 8), block(64);
+  if (h->pi_pend)
+    hipLaunchKernelGGL(k_plant_sens_pi, grid, block, 0, h->stream, h->K, (const double*)h->d_th_pend, h->B, h->Bp, x_dev, u_dev, h->K.o.t_step,
+                       n_sub, theta ? 1 : 0, h->d_psn_planes);
+  else
+    hipLaunchKernelGGL(k_plant_sens, grid, block, 0, h->stream, h->K, h->B, h->Bp, x_dev, u_dev, h->K.o.t_step, n_sub, theta ? 1 : 0,
+                       h->d_psn_planes);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// planes [f0 .. f0 + F)[Bp] -> row-major B x F at out_dev
+int planes_to_rows(ltompc_solver* h, const double* planes, const int f0, const int F, double* out_dev) {
+  const size_t n = (size_t)h->B * F;
+  hipLaunchKernelGGL(k_planes_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, planes, f0, F, h->B, h->Bp, out_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -900,7 +947,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   hipLaunchKernelGGL(k_psens_keep_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, h->d_psens_uprev, (const int*)(h->packed ? h->d_orig : nullptr));
   hipLaunchKernelGGL(k_store_u0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, u0_dev, (const int*)(h->packed ? h->d_orig : nullptr));
   HIPCHECK(hipGetLastError());
-  h->psens_uprev = true;
+  h->psens_uprev = true, h->loop_fresh = true;
   h->last_launches = L.launches + 3;
   h->last_iterations = it + 1;
   h->sens_state = 1;
@@ -1332,6 +1379,125 @@ int ltompc_plant_step(ltompc_handle h, const double* x, const double* u, int n_s
   if (rc) return rc;
   HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * h->B, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_plant_sensitivities_dev(ltompc_handle h, const double* x_dev, const double* u_dev, int n_sub, double* x_next_dev, double* dxn_dx_dev,
+                                   double* dxn_du_dev, double* dxn_dtheta_dev) {
+  const char* who = "ltompc_plant_sensitivities";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x_dev || !u_dev) return fail(std::string(who) + ": null argument");
+  if (dxn_dtheta_dev && h->K.p.ptv != 0.0) return fail(std::string(who) + ": dxn_dtheta is not available with torque vectoring (ptv != 0)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psn_prepare(h, false)) return -1;
+  if (dxn_dx_dev || dxn_du_dev || dxn_dtheta_dev) {
+    if (psn_launch(h, x_dev, u_dev, n_sub, dxn_dtheta_dev != nullptr)) return -1;
+    if (dxn_dx_dev && planes_to_rows(h, h->d_psn_planes, PSN_DX, 64, dxn_dx_dev)) return -1;
+    if (dxn_du_dev && planes_to_rows(h, h->d_psn_planes, PSN_DU, 16, dxn_du_dev)) return -1;
+    if (dxn_dtheta_dev && planes_to_rows(h, h->d_psn_planes, PSN_DTH, 8 * PS_NT, dxn_dtheta_dev)) return -1;
+  }
+  if (x_next_dev) return ltompc_plant_step_dev(h, x_dev, u_dev, n_sub, x_next_dev);  // (k_plant itself: the plant's bits)
+  return 0;
+}
+
+int ltompc_plant_sensitivities(ltompc_handle h, const double* x, const double* u, int n_sub, double* x_next, double* dxn_dx, double* dxn_du,
+                               double* dxn_dtheta) {
+  const char* who = "ltompc_plant_sensitivities";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x || !u) return fail(std::string(who) + ": null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psn_prepare(h, false)) return -1;
+  const size_t B = h->B;
+  double *dx = h->d_io, *du = h->d_io + 8 * (size_t)h->Bp, *dn = h->d_io + 10 * (size_t)h->Bp;
+  double *rx = h->d_psn_rm, *ru = rx + 64 * B, *rt = ru + 16 * B;
+  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * B, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(du, u, sizeof(double) * 2 * B, hipMemcpyHostToDevice, h->stream));
+  if (ltompc_plant_sensitivities_dev(h, dx, du, n_sub, x_next ? dn : nullptr, dxn_dx ? rx : nullptr, dxn_du ? ru : nullptr,
+                                     dxn_dtheta ? rt : nullptr))
+    return -1;
+  if (x_next) HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, h->stream));
+  if (dxn_dx) HIPCHECK(hipMemcpyAsync(dxn_dx, rx, sizeof(double) * 64 * B, hipMemcpyDeviceToHost, h->stream));
+  if (dxn_du) HIPCHECK(hipMemcpyAsync(dxn_du, ru, sizeof(double) * 16 * B, hipMemcpyDeviceToHost, h->stream));
+  if (dxn_dtheta) HIPCHECK(hipMemcpyAsync(dxn_dtheta, rt, sizeof(double) * 8 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_loop_begin(ltompc_handle h, int mode) {
+  const char* who = "ltompc_loop_begin";
+  if (!h) return fail("null handle");
+  if (mode < 1 || mode > 3) return fail(std::string(who) + ": mode must be 1 (theta enters the controller), 2 (the plant) or 3 (both)");
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psn_prepare(h, true)) return -1;
+  const int B = h->B, Bp = h->Bp;
+  hipLaunchKernelGGL(k_loop_begin, dim3((LOOP_NQ * Bp + 255) / 256), dim3(256), 0, h->stream, B, Bp, h->d_loop_Sx, h->d_loop_Du, h->d_loop_ok,
+                     h->d_loop_ticks);
+  HIPCHECK(hipGetLastError());
+  h->loop_mode = mode, h->loop_active = true;
+  return 0;
+}
+
+int ltompc_loop_tick_dev(ltompc_handle h, const double* x_dev, const double* u0_dev, int n_sub, double* x_next_dev) {
+  const char* who = "ltompc_loop_tick";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x_dev || !u0_dev || !x_next_dev) return fail(std::string(who) + ": null argument");
+  if (!h->loop_active) return fail(std::string(who) + ": no loop (ltompc_loop_begin first)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (sens_compute(h, false, who)) return -1;  // (the usage error after set_initial_guess comes from here)
+  if (!h->psens_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");
+  if (!h->loop_fresh) return fail(std::string(who) + ": no new solve since the last tick (make_step or make_step_dev first)");
+  const int mode = h->loop_mode;
+  if ((mode & 1) && psens_compute(h, false, who)) return -1;
+  if (psn_launch(h, x_dev, u0_dev, n_sub, (mode & 2) != 0)) return -1;
+  hipLaunchKernelGGL(k_loop_accum, dim3((LOOP_NQ * h->Bp + 255) / 256), dim3(256), 0, h->stream, h->B, h->Bp, mode, (const double*)h->d_sens_du0,
+                     (const double*)((mode & 1) ? h->d_psens_du0 : nullptr), (const int*)h->d_sens_ok, (const double*)h->d_psn_planes, h->d_loop_Sx,
+                     h->d_loop_Du, h->d_loop_ok, h->d_loop_ticks);
+  HIPCHECK(hipGetLastError());
+  h->loop_fresh = false;
+  return ltompc_plant_step_dev(h, x_dev, u0_dev, n_sub, x_next_dev);
+}
+
+int ltompc_loop_tick(ltompc_handle h, const double* x, const double* u0, int n_sub, double* x_next) {
+  const char* who = "ltompc_loop_tick";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x || !u0 || !x_next) return fail(std::string(who) + ": null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  double *dx = h->d_io, *du = h->d_io + 8 * (size_t)h->Bp, *dn = h->d_io + 10 * (size_t)h->Bp;
+  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * h->B, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(du, u0, sizeof(double) * 2 * h->B, hipMemcpyHostToDevice, h->stream));
+  if (ltompc_loop_tick_dev(h, dx, du, n_sub, dn)) return -1;
+  HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * h->B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_get_loop_sensitivities(ltompc_handle h, double* dx_dq, double* du_dq, int* ok, int* ticks) {
+  if (!h) return fail("null handle");
+  if (!h->d_loop_Sx) return fail("ltompc_get_loop_sensitivities: no loop (ltompc_loop_begin first)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_loop_ok, sizeof(int) * h->B, hipMemcpyDeviceToHost, h->stream));
+  if (ticks) HIPCHECK(hipMemcpyAsync(ticks, h->d_loop_ticks, sizeof(int) * h->B, hipMemcpyDeviceToHost, h->stream));
+  if (planes_to_host(h, h->d_loop_Sx, 8 * LOOP_NQ, 1, dx_dq)) return -1;
+  if (planes_to_host(h, h->d_loop_Du, 2 * LOOP_NQ, 1, du_dq)) return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_loop_sensitivities_dev(ltompc_handle h, double* dx_dq_dev, double* du_dq_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  if (!h->d_loop_Sx) return fail("ltompc_loop_sensitivities_dev: no loop (ltompc_loop_begin first)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (dx_dq_dev && planes_to_rows(h, h->d_loop_Sx, 0, 8 * LOOP_NQ, dx_dq_dev)) return -1;
+  if (du_dq_dev && planes_to_rows(h, h->d_loop_Du, 0, 2 * LOOP_NQ, du_dq_dev)) return -1;
+  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_loop_ok, sizeof(int) * h->B, hipMemcpyDeviceToDevice, h->stream));
+  return 0;
+}
+
+int ltompc_loop_end(ltompc_handle h) {
+  if (!h) return fail("null handle");
+  h->loop_active = false;
   return 0;
 }
 

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NTHETA, NX, NU, THETA_NAMES, Options, Params, check, dptr, iptr, lib
+from ._lib import LOOP_NAMES, NLOOP, NTHETA, NX, NU, THETA_NAMES, Options, Params, check, dptr, iptr, lib
 from .tables import TrackTables
 
 KERNEL_CLASSES = ("eval", "riccati", "expand", "linesearch", "pick", "update", "riccati1", "step1")  # include/ltompc.h
@@ -186,6 +186,60 @@ class BatchedMPC:
         """Enqueue a copy of the last solve's prediction into device arrays (B,N+1,8) / (B,N,2) of doubles in the caller's
         order, on the handle's stream (prediction() without the host; the instances stay packed as they are)."""
         check(lib().ltompc_get_prediction_dev(self._h, C.c_void_p(X_ptr or None), C.c_void_p(U_ptr or None)))
+
+    # ---- plant-step and closed-loop sensitivities (ltompc_plant_sensitivities, ltompc_loop_*, DESIGN.md §12) ---------------
+    def plant_sensitivities(self, x, u, n_sub: int = 400, theta: bool = True):
+        """The plant step and the derivative of its discrete RK4 map at (x (B,8), u (B,2)): x_next (B,8, the bits of
+        plant_step), dx (B,8,8), du (B,8,2) and, with theta=True, dtheta (B,8,16; columns THETA_NAMES, the cost columns 0);
+        names.  With per-instance rows: at the rows in effect, as plant_step."""
+        x, u = self._x(x), np.ascontiguousarray(np.asarray(u, float).reshape(self.B, NU))
+        xn, dx, du = np.empty_like(x), np.empty((self.B, NX, NX)), np.empty((self.B, NX, NU))
+        dth = np.empty((self.B, NX, NTHETA)) if theta else None
+        check(lib().ltompc_plant_sensitivities(self._h, dptr(x), dptr(u), int(n_sub), dptr(xn), dptr(dx), dptr(du),
+                                               dptr(dth) if theta else None))
+        out = dict(x_next=xn, dx=dx, du=du, names=THETA_NAMES)
+        if theta:
+            out["dtheta"] = dth
+        return out
+
+    def plant_sensitivities_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int = 0, dx_ptr: int = 0, du_ptr: int = 0, dtheta_ptr: int = 0,
+                                n_sub: int = 400):
+        """Enqueue plant_sensitivities on the handle's stream: device arrays x (B,8), u (B,2) in; x_next (B,8), dx (B,8,8),
+        du (B,8,2), dtheta (B,8,16) out (0: not wanted)."""
+        check(lib().ltompc_plant_sensitivities_dev(self._h, C.c_void_p(x_ptr), C.c_void_p(u_ptr), int(n_sub), C.c_void_p(xn_ptr or None),
+                                                   C.c_void_p(dx_ptr or None), C.c_void_p(du_ptr or None), C.c_void_p(dtheta_ptr or None)))
+
+    def loop_begin(self, mode: int = 3):
+        """Start accumulating the closed-loop sensitivities dx_t/dq, q = (x_init, theta): mode bit 1 - theta enters the
+        controller, bit 2 - theta enters the plant."""
+        check(lib().ltompc_loop_begin(self._h, int(mode)))
+
+    def loop_tick_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int, n_sub: int = 400):
+        """After make_step(_dev) at x that gave u: the plant step into xn (as plant_step_dev) and one tick of the accumulation,
+        enqueued on the handle's stream."""
+        check(lib().ltompc_loop_tick_dev(self._h, C.c_void_p(x_ptr), C.c_void_p(u_ptr), int(n_sub), C.c_void_p(xn_ptr)))
+
+    def loop_tick(self, x, u0, n_sub: int = 400):
+        """Host form of loop_tick_dev; returns x_next (B,8)."""
+        x, u0 = self._x(x), np.ascontiguousarray(np.asarray(u0, float).reshape(self.B, NU))
+        xn = np.empty_like(x)
+        check(lib().ltompc_loop_tick(self._h, dptr(x), dptr(u0), int(n_sub), dptr(xn)))
+        return xn
+
+    def loop_sensitivities(self):
+        """dx (B,8,24) = dx_t/dq and du (B,2,24) = du_{t-1}/dq after the ticks so far, columns names = LOOP_NAMES (x_init[0..7],
+        then THETA_NAMES); ok (B,) bool, ticks (B,) (the ticks accumulated while ok).  Where ok is False dx and du are 0."""
+        dx, du = np.empty((self.B, NX, NLOOP)), np.empty((self.B, NU, NLOOP))
+        ok, ticks = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        check(lib().ltompc_get_loop_sensitivities(self._h, dptr(dx), dptr(du), iptr(ok), iptr(ticks)))
+        return dict(dx=dx, du=du, ok=ok != 0, ticks=ticks, names=LOOP_NAMES)
+
+    def loop_sensitivities_dev(self, dx_ptr: int = 0, du_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue a copy of the loop sensitivities into device arrays (B,8,24) / (B,2,24) doubles / (B,) int32."""
+        check(lib().ltompc_loop_sensitivities_dev(self._h, C.c_void_p(dx_ptr or None), C.c_void_p(du_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    def loop_end(self):
+        check(lib().ltompc_loop_end(self._h))
 
     def theta(self):
         """The handle's values of the 16 parameters of param_sensitivities(), in THETA_NAMES order."""
@@ -481,13 +535,15 @@ class SplitMPC:
     def make_step_dev(self, x0_ptr: int, u0_ptr: int):
         self._each(lambda p, lo, hi: p.make_step_dev(x0_ptr + 8 * NX * lo, u0_ptr + 8 * NU * lo))
 
-    def run_ticks(self, x_ptr: int, u_ptr, xn_ptr: int, n_ticks: int, n_sub: int = 400, after_tick=None, before_tick=None):
+    def run_ticks(self, x_ptr: int, u_ptr, xn_ptr: int, n_ticks: int, n_sub: int = 400, after_tick=None, before_tick=None,
+                  loop: bool = False):
         """n_ticks of the closed loop [make_step; plant step] for every part at its own pace: x (B, 8) and xn (B, 8) are swapped
         after every tick (the states end in x if n_ticks is even, else in xn), u (B, 2) holds the last controls.  u_ptr may be a
         sequence of pointers: tick t then writes its controls to u_ptr[t % len(u_ptr)] (a ring: somebody else - a gather over the
         ranks, a logger - reads the controls of tick t while the parts are one tick further).
         before_tick(part_index, tick) / after_tick(part_index, tick) run in the part's thread around each of its ticks (before_tick
-        may block: that is how a consumer of the ring holds a part back).  Returns when all parts are done."""
+        may block: that is how a consumer of the ring holds a part back).  loop=True: loop_tick_dev in place of plant_step_dev
+        (after loop_begin): the same states, and the closed-loop sensitivities accumulate.  Returns when all parts are done."""
         ring = [int(u_ptr)] if isinstance(u_ptr, int) else [int(q) for q in u_ptr]
         def body(p, lo, hi):
             a, b = x_ptr + 8 * NX * lo, xn_ptr + 8 * NX * lo
@@ -497,7 +553,7 @@ class SplitMPC:
                     before_tick(pi, t)
                 u = ring[t % len(ring)] + 8 * NU * lo
                 p.make_step_dev(a, u)
-                p.plant_step_dev(a, u, b, n_sub)
+                (p.loop_tick_dev if loop else p.plant_step_dev)(a, u, b, n_sub)
                 a, b = b, a
                 if after_tick is not None:
                     after_tick(pi, t)
@@ -589,6 +645,48 @@ class SplitMPC:
             p.adjoint_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0,
                           grad_p_ptr + 8 * 10 * lo if grad_p_ptr else 0, grad_theta_ptr + 8 * NTHETA * lo if grad_theta_ptr else 0,
                           ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def plant_sensitivities(self, x, u, n_sub: int = 400, theta: bool = True):
+        """BatchedMPC.plant_sensitivities of every part on its rows, stitched in the caller's order."""
+        x, u = np.asarray(x, dtype=np.float64).reshape(self.B, NX), np.asarray(u, dtype=np.float64).reshape(self.B, NU)
+        r = [p.plant_sensitivities(x[lo:hi], u[lo:hi], n_sub, theta) for p, (lo, hi) in zip(self.parts, self.bounds)]
+        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+
+    def plant_sensitivities_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int = 0, dx_ptr: int = 0, du_ptr: int = 0, dtheta_ptr: int = 0,
+                                n_sub: int = 400):
+        """BatchedMPC.plant_sensitivities_dev of every part on its rows, each on its part's stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.plant_sensitivities_dev(x_ptr + 8 * NX * lo, u_ptr + 8 * NU * lo, xn_ptr + 8 * NX * lo if xn_ptr else 0,
+                                      dx_ptr + 8 * NX * NX * lo if dx_ptr else 0, du_ptr + 8 * NX * NU * lo if du_ptr else 0,
+                                      dtheta_ptr + 8 * NX * NTHETA * lo if dtheta_ptr else 0, n_sub)
+
+    def loop_begin(self, mode: int = 3):
+        for p in self.parts:
+            p.loop_begin(mode)
+
+    def loop_tick_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int, n_sub: int = 400):
+        """BatchedMPC.loop_tick_dev of every part on its rows of x (B,8), u (B,2), xn (B,8), each on its part's stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.loop_tick_dev(x_ptr + 8 * NX * lo, u_ptr + 8 * NU * lo, xn_ptr + 8 * NX * lo, n_sub)
+
+    def loop_tick(self, x, u0, n_sub: int = 400):
+        x, u0 = np.asarray(x, dtype=np.float64).reshape(self.B, NX), np.asarray(u0, dtype=np.float64).reshape(self.B, NU)
+        return np.concatenate([p.loop_tick(x[lo:hi], u0[lo:hi], n_sub) for p, (lo, hi) in zip(self.parts, self.bounds)])
+
+    def loop_sensitivities(self):
+        """BatchedMPC.loop_sensitivities of every part, stitched in the caller's order."""
+        r = [p.loop_sensitivities() for p in self.parts]
+        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+
+    def loop_sensitivities_dev(self, dx_ptr: int = 0, du_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.loop_sensitivities_dev of every part into its rows of (B,8,24) / (B,2,24) doubles / (B,) int32."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.loop_sensitivities_dev(dx_ptr + 8 * NX * NLOOP * lo if dx_ptr else 0, du_ptr + 8 * NU * NLOOP * lo if du_ptr else 0,
+                                     ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def loop_end(self):
+        for p in self.parts:
+            p.loop_end()
 
     def prediction_dev(self, X_ptr: int = 0, U_ptr: int = 0):
         """BatchedMPC.prediction_dev of every part into its rows of (B,N+1,8) / (B,N,2) doubles, each on its part's stream."""
