@@ -87,6 +87,21 @@ __device__ __forceinline__ void lin8(const Consts& K, const Work& W, E8Lds& L, c
   for (int q = 0; q < 9; q++) L.r2[i * 9 + q] = 0.0;  // Hc, Hx+
   L.misc[i] = 0.0;
   WAVE_SYNC();
+#if defined(LTOMPC_HARNESS_WAVEFRONT)
+  // tests/host_harness: the model functions ADD terms to their outputs, and the four lanes of a half add the same term to the same
+  // LDS word in the same instruction - on the device every one of them reads the old value and stores the same new one.  The
+  // harness's lanes run one after the other between two collectives and would add four times: there only the first lane of a half
+  // works on the LDS, the other three on a private copy that starts, like the LDS words, from zeros.
+  {
+    double f[8], own[48 + 36 + 8];
+    for (int q = 0; q < 48 + 36 + 8; q++) own[q] = 0.0;
+    const bool first = (i & 3) == 0;
+    double* const Hh = first ? &L.r2[pt * 36] : own + 48;
+    rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, px, f, first ? &L.r1[pt * 48] : own, lam, hdt, Hh);
+    for (int q = 0; q < 6; q++) L.r2[72 + pt * 8 + q] = f[q];
+    S.cost = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, k == N - 1, pt ? (first ? &L.misc[0] : own + 84) : &L.vec[0], pt ? Hh : &L.vec[8]);
+  }
+#else
   {
     double f[8];
     rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, px, f, &L.r1[pt * 48], lam, hdt, &L.r2[pt * 36]);
@@ -94,6 +109,7 @@ __device__ __forceinline__ void lin8(const Consts& K, const Work& W, E8Lds& L, c
     for (int q = 0; q < 6; q++) L.r2[72 + pt * 8 + q] = f[q];
   }
   S.cost = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, k == N - 1, pt ? &L.misc[0] : &L.vec[0], pt ? &L.r2[36] : &L.vec[8]);
+#endif
   S.nl = (k + 1 <= N - 1);
   double hss[3] = {0, 0, 0}, hmm[3] = {0, 0, 0};
   if (S.nl) {

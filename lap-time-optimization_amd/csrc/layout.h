@@ -175,14 +175,18 @@ struct Consts {
 
 // no s_barrier and, unlike __syncthreads(), must not drain the outstanding global loads/stores (vmcnt): only the
 // compiler has to keep the LDS accesses in order.
+#if defined(LTOMPC_HARNESS_WAVEFRONT)  // (a wave-level collective of the harness's lock-step wavefront, hip_shim.h; a shim without one makes the builtins below no-ops)
+#define WAVE_SYNC() lt_wave_sync(__FILE__, __LINE__)
+#else
 #define WAVE_SYNC()                                        \
   do {                                                     \
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
     __builtin_amdgcn_wave_barrier();                       \
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
   } while (0)
+#endif
 
-#if !defined(LTOMPC_HOST_HARNESS)  // (the harness brings its own: 8 OS threads and a barrier, hip_shim.h)
+#if !defined(LTOMPC_HOST_HARNESS)  // (the harness brings its own, as group-level collectives of its lock-step wavefront: hip_shim.h)
 __device__ __forceinline__ double grp_max(double v) {  // over the 8 lanes of an instance (lane stride 8)
   v = fmax(v, __shfl_xor(v, 8)), v = fmax(v, __shfl_xor(v, 16)), v = fmax(v, __shfl_xor(v, 32));
   return v;
@@ -196,7 +200,7 @@ __device__ __forceinline__ double grp_min(double v) {
   return v;
 }
 
-#else
+#elif !defined(LTOMPC_HARNESS_WAVEFRONT)  // (a shim without the lock-step wavefront: plain functions of the global namespace)
 using ::grp_max;
 using ::grp_min;
 using ::grp_sum;

@@ -1632,8 +1632,10 @@ __global__ void __launch_bounds__(256) k_riccati1q(Consts K, Work W, Launch la, 
 // One wavefront per instance (narrow launches: once few instances are left, a launch is as long as one wavefront's
 // sweep, and 8 instances per wavefront make that sweep ~3x longer than it has to be).  Dynamic LDS: ric1_lds_bytes(N).
 __global__ void __launch_bounds__(64) k_riccati1(Consts K, Work W, Launch la, int it_index, int max_sweeps) {
-#if defined(LTOMPC_HOST_HARNESS)
-  static double lds1[1];  // (never run by the harness)
+#if defined(LTOMPC_HARNESS_WAVEFRONT)
+  double* const lds1 = static_cast<double*>(lt_dyn_lds);  // ric1_lds_bytes(N) at its exact size, allocated per block by the harness
+#elif defined(LTOMPC_HOST_HARNESS)
+  static double lds1[1];  // (a shim without the lock-step wavefront never runs this)
 #else
   extern __shared__ double lds1[];
 #endif
@@ -1667,8 +1669,10 @@ __global__ void __launch_bounds__(256) k_riccati1q_pi(Consts K, WorkPI W, Launch
 #endif
 }
 __global__ void __launch_bounds__(64) k_riccati1_pi(Consts K, WorkPI W, Launch la, int it_index, int max_sweeps) {
-#if defined(LTOMPC_HOST_HARNESS)
-  static double lds1[1];  // (never run by the harness)
+#if defined(LTOMPC_HARNESS_WAVEFRONT)
+  double* const lds1 = static_cast<double*>(lt_dyn_lds);  // ric1_lds_bytes(N) at its exact size, allocated per block by the harness
+#elif defined(LTOMPC_HOST_HARNESS)
+  static double lds1[1];  // (a shim without the lock-step wavefront never runs this)
 #else
   extern __shared__ double lds1[];
 #endif

@@ -1,7 +1,15 @@
-"""The solver's device code as host C++ under AddressSanitizer + UndefinedBehaviorSanitizer (tests/host_harness):
-the thread-per-slot kernels (k_init, k_eval, k_expand, k_linesearch, k_pick, k_update, k_plant, ...) and the serial Riccati
-kernel run whole interior-point solves on the CPU with every work buffer NaN-poisoned and allocated at its exact size; any
-out-of-bounds access or undefined operation aborts the run, a read of a never-written word shows up as a NaN result.
+"""The solver's device code as host C++ under AddressSanitizer + UndefinedBehaviorSanitizer (tests/host_harness): whole
+interior-point solves on the CPU with every work buffer NaN-poisoned and allocated at its exact size; any out-of-bounds access or
+undefined operation aborts the run, a read of a never-written word shows up as a NaN result.
+
+This file: the thread-per-slot kernels (k_init, k_eval, k_expand, k_linesearch, k_update, k_plant, ...) with the serial Riccati
+kernel (the LTOMPC_RICCATI=serial path) and k_pick on the harness's lock-step wavefront.  test_host_harness_wave.py, with the
+same fixture: the wave kernels k_riccati8, k_riccati1, k_eval8 / k_expand8, k_sens_eval8, k_sens_riccati8, k_sens_forward,
+k_psens_sweep, k_adj_sweep, the thread-per-slot kernels of the derivative passes (k_sens_eval, k_psens_cond, k_plant_sens,
+k_planes_rows, k_loop_begin, k_loop_accum, k_theta_rows, k_slip_forces, k_test_ellipse, k_velocity_profile) and every _pi form.
+Still left out, because their workgroups have several wavefronts: k_riccati1q, k_step1, the packing kernels k_compact / k_pack*,
+the rollout kernels.
+
 The numbers are compared with the oracle (the GPU library's own results are compared with the oracle in test_gpu_parity.py).
 Test infrastructure only: the package never builds or loads this."""
 import os
@@ -27,17 +35,32 @@ def harness():
     return EXE
 
 
-def _run(exe, tmp_path, tables, x0, N, any_bounds=0, soft_rho=0.0, ticks=2, ell=(0.0, 0.0, 0.0, 0.0), **options):
+def _run(exe, tmp_path, tables, x0, N, any_bounds=0, soft_rho=0.0, ticks=2, ell=(0.0, 0.0, 0.0, 0.0), rows=None, cot=None, u=None, args=(),
+         **options):
+    """rows: B x 16 per-instance rows (section `rows` of the problem file); cot: a list of cotangents (gX (B,N+1,8), gU (B,N,2))
+    for the adjoint sweeps of derivs=1; u: B x 2 controls for plant_sens=<n_sub>; args: further key=value arguments as they are
+    (param.<field>=...); options: key=value arguments (a string as it is: riccati="8", eval="slot")."""
     prob = tmp_path / "problem.txt"
     tab = tables.packed()
     with open(prob, "w") as f:
         f.write(f"{tab.shape[1]} {N} {x0.shape[0]} {any_bounds} {soft_rho!r} {ticks} {ell[0]!r} {ell[1]!r} {ell[2]!r} {ell[3]!r}\n")
         np.savetxt(f, tab.ravel()[None], fmt="%.17g")
         np.savetxt(f, x0.ravel()[None], fmt="%.17g")
+        if rows is not None:
+            f.write("rows\n")
+            np.savetxt(f, np.asarray(rows, dtype=np.float64).ravel()[None], fmt="%.17g")
+        if u is not None:
+            f.write("u\n")
+            np.savetxt(f, np.asarray(u, dtype=np.float64).ravel()[None], fmt="%.17g")
+        if cot:
+            f.write(f"cot {len(cot)}\n")
+            for gX, gU in cot:
+                np.savetxt(f, np.concatenate([np.ravel(gX), np.ravel(gU)])[None], fmt="%.17g")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe, str(prob)] + [f"{k}={v!r}" for k, v in options.items()], capture_output=True, text=True, env=env, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]   # a sanitizer report ends the process with a non-zero code
-    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-3000:]
+    argv = [exe, str(prob)] + [f"{k}={v if isinstance(v, str) else repr(v)}" for k, v in options.items()] + list(args)
+    out = subprocess.run(argv, capture_output=True, text=True, env=env, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]   # a sanitizer report or a mismatched collective ends the process with a non-zero code
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr and "MISMATCHED" not in out.stderr, out.stderr[-3000:]
     res, cur = [], None
     for line in out.stdout.splitlines():
         if line.startswith("tick"):
