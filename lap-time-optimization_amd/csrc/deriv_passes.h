@@ -1,0 +1,382 @@
+// deriv_passes.h — host drivers and C entry points of the derivative passes on the final iterate of a solve:
+// sensitivities w.r.t. (x0, u_prev) and theta, the adjoint of a trajectory loss, the plant-step sensitivities and the closed loop.
+// Part of ltompc.hip's translation unit, after ltompc_solver and its helpers; the passes' state is ltompc_solver::dv (DerivState).
+#pragma once
+
+namespace {
+
+constexpr hipMemcpyKind D2H = hipMemcpyDeviceToHost, D2D = hipMemcpyDeviceToDevice;
+
+// n elements to an output of a C entry point, host or device by `kind`; dst may be null (an output the caller does not ask for)
+template <typename T>
+int copy_out(ltompc_solver* h, const hipMemcpyKind kind, T* dst, const T* src, const size_t n) {
+  if (dst) HIPCHECK(hipMemcpyAsync(dst, src, n * sizeof(T), kind, h->stream));
+  return 0;
+}
+
+// The re-linearisation and head-less sweep of the sensitivity passes (sensitivity.h), shared by all of them: run once per solve,
+// and again only when the instances have moved since (same blocks, same bits, at their new slots).  The uniform kernels on Ws or
+// the _pi ones on its WorkPI form (at each instance's rows of that solve, TH); the evaluation kernels the solve used.
+void sens_factorise(ltompc_solver* h) {
+  DerivState& D = h->dv;
+  if (D.fact) return;
+  const int N = h->N, Bp = h->Bp;
+  const bool ref = h->ref_eval, ell = h->K.bd.nel > 0;
+  const auto run = [&](auto eval8, auto eval, auto riccati8, auto* d_W, const auto& W) {
+    if (h->eval8) hipLaunchKernelGGL(eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, d_W);
+    else hipLaunchKernelGGL(eval, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, (const Consts*)h->d_K, d_W);
+    hipLaunchKernelGGL(riccati8, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, W, (const int*)h->W.si, D.d_sens_inertia);
+  };
+  if (h->pi_solve)
+    run(k_sens_eval8_pi, ref ? k_sens_eval_pi<BoundsRef> : k_sens_eval_pi<BoundsAny>, k_sens_riccati8_pi, (const WorkPI*)D.d_Wspi, D.Wspi);
+  else
+    run(k_sens_eval8, ell ? (ref ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
+                          : (ref ? k_sens_eval<BoundsRef, false> : k_sens_eval<BoundsAny, false>),
+        k_sens_riccati8, (const Work*)D.d_Ws, D.Ws);
+  D.fact = true;
+}
+
+// The sensitivity pass of the last solve (sensitivity.h), enqueued on the handle's stream: linearisation and head-less sweep
+// when not done since that solve (or when the instances have moved since), the forward pass for du0 / ok / margin, and the
+// trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
+int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
+  DerivState& D = h->dv;
+  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess discards the last solve)");
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!D.d_Ws) {
+    Work& Ws = D.Ws = h->W;
+    int rc = 0;
+    rc |= h->dalloc(&Ws.QP, (size_t)QP_NF * (N + 1) * Bp, true), rc |= h->dalloc(&Ws.RC, (size_t)RC_NF * (N + 1) * Bp, true);
+    rc |= h->dalloc(&Ws.RS, (size_t)RS_NF * N * Bp, true), rc |= h->dalloc(&Ws.LS, (size_t)3 * N * Bp, true);
+    rc |= h->dalloc(&Ws.si, (size_t)SI_NF * Bp);  // zeros, never written
+    rc |= h->dalloc(&D.d_sens_inertia, Bp), rc |= h->dalloc(&D.d_sens_ok, Bp);
+    rc |= h->dalloc(&D.d_sens_du0, (size_t)2 * SENS_NP * B), rc |= h->dalloc(&D.d_sens_margin, B);
+    rc |= h->dalloc(&D.d_Ws, 1);
+    if (rc) return -1;
+    HIPCHECK(hipMemcpyAsync(D.d_Ws, &D.Ws, sizeof(Work), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if (h->d_th_solve && sync_pi_work(h)) return -1;
+  }
+  if (D.sens == Sens::solved) {
+    sens_factorise(h);
+    hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, D.Ws, (const int*)D.d_sens_inertia, h->K.bd.ni, D.d_sens_du0,
+                       D.d_sens_ok, D.d_sens_margin, (double*)nullptr, (double*)nullptr, (const int*)nullptr);
+    D.sens = Sens::du0;
+  }
+  if (traj && D.sens == Sens::du0) {
+    if (!D.d_sens_dX && (h->dalloc(&D.d_sens_dX, (size_t)(N + 1) * 8 * SENS_NP * B) || h->dalloc(&D.d_sens_dU, (size_t)N * 2 * SENS_NP * B)))
+      return -1;
+    sens_factorise(h);
+    hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, D.Ws, (const int*)D.d_sens_inertia, h->K.bd.ni, (double*)nullptr,
+                       (int*)nullptr, (double*)nullptr, D.d_sens_dX, D.d_sens_dU, (const int*)D.d_sens_ok);
+    D.sens = Sens::traj;
+  }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// What both passes over theta need: a problem that theta covers, a solve to differentiate whose u_prev was kept, the PV buffers.
+int psens_prepare(ltompc_solver* h, const char* who) {
+  DerivState& D = h->dv;
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  if (sens_compute(h, false, who)) return -1;  // (the usage error before a solve comes from here)
+  if (!D.kept_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!D.d_psens_pv && (h->dalloc(&D.d_psens_pv, (size_t)PV_NF * N * Bp, true) || h->dalloc(&D.d_psens_kf, (size_t)N * 2 * PS_NT * Bp, true) ||
+                        h->dalloc(&D.d_psens_du0, (size_t)2 * PS_NT * B)))
+    return -1;
+  return 0;
+}
+
+// The factorisation and k_psens_cond's PV planes at the instances' current slots, each only when not there already (both passes
+// that read the planes come through here).
+void psens_condense(ltompc_solver* h) {
+  DerivState& D = h->dv;
+  sens_factorise(h);
+  if (D.pv_valid) return;
+  const int N = h->N, Bp = h->Bp;
+  if (h->pi_solve)
+    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond_pi<BoundsRef> : k_psens_cond_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                       (const Consts*)h->d_K, (const WorkPI*)h->d_Wpi, D.d_psens_pv);
+  else
+    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
+                       (const Consts*)h->d_K, (const Work*)h->d_W, D.d_psens_pv);
+  D.pv_valid = true;
+}
+
+// The parameter-sensitivity pass of the last solve (param_sensitivity.h): ok (and du0 / margin) of the pass above, whose
+// factorisation it shares, then the condensed right-hand sides of the 16 columns and their recursion.  Cached like the above.
+int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
+  DerivState& D = h->dv;
+  if (psens_prepare(h, who)) return -1;
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (traj && !D.d_psens_dX && (h->dalloc(&D.d_psens_dX, (size_t)(N + 1) * 8 * PS_NT * B) || h->dalloc(&D.d_psens_dU, (size_t)N * 2 * PS_NT * B)))
+    return -1;
+  if (D.psens == Psens::none || (traj && D.psens == Psens::du0)) {
+    psens_condense(h);
+    double *const dX = traj ? D.d_psens_dX : nullptr, *const dU = traj ? D.d_psens_dU : nullptr;
+    if (h->pi_solve)
+      hipLaunchKernelGGL(k_psens_sweep_pi, dim3(Bp / 8, 2), dim3(64), 0, h->stream, D.Wspi, (const double*)D.d_psens_uprev,
+                         (const double*)D.d_psens_pv, (const int*)D.d_sens_ok, D.d_psens_kf, D.d_psens_du0, dX, dU);
+    else
+      hipLaunchKernelGGL(k_psens_sweep, dim3(Bp / 8, 2), dim3(64), 0, h->stream, D.Ws, h->K.p.r_du[0], h->K.p.r_du[1],
+                         (const double*)D.d_psens_uprev, (const double*)D.d_psens_pv, (const int*)D.d_sens_ok, D.d_psens_kf, D.d_psens_du0, dX, dU);
+    D.psens = traj ? Psens::traj : Psens::du0;
+  }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The adjoint pass of the last solve (adjoint.h) for one cotangent (device pointers, caller's order; either may be null), into
+// d_adj_gp and, with theta, d_adj_gth: the factorisation and the PV planes when not there, then one sweep.  Once its buffers
+// exist it only enqueues.
+int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, const bool theta, const char* who) {
+  DerivState& D = h->dv;
+  if (!gX_dev && !gU_dev) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  if (theta ? psens_prepare(h, who) : sens_compute(h, false, who)) return -1;
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!D.d_adj_gp && (h->dalloc(&D.d_adj_gp, (size_t)ADJ_NP * B) || h->dalloc(&D.d_adj_gth, (size_t)PS_NT * B))) return -1;
+  if (theta && !D.d_adj_aj && h->dalloc(&D.d_adj_aj, (size_t)AJ_NF * N * Bp, true)) return -1;
+  theta ? psens_condense(h) : sens_factorise(h);
+  double* const gth = theta ? D.d_adj_gth : nullptr;
+  if (h->pi_solve)
+    hipLaunchKernelGGL(k_adj_sweep_pi, dim3(Bp / 8), dim3(64), 0, h->stream, D.Wspi, (const double*)D.d_psens_uprev, (const double*)D.d_psens_pv,
+                       (const int*)D.d_sens_ok, gX_dev, gU_dev, D.d_adj_aj, D.d_adj_gp, gth);
+  else
+    hipLaunchKernelGGL(k_adj_sweep, dim3(Bp / 8), dim3(64), 0, h->stream, D.Ws, h->K.p.r_du[0], h->K.p.r_du[1], (const double*)D.d_psens_uprev,
+                       (const double*)D.d_psens_pv, (const int*)D.d_sens_ok, gX_dev, gU_dev, D.d_adj_aj, D.d_adj_gp, gth);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// k_plant_sens' planes and the row-major staging of the host forms and, with `loop`, the closed loop's state: each on the first
+// request, with one synchronisation.
+int psn_prepare(ltompc_solver* h, const bool loop) {
+  DerivState& D = h->dv;
+  int rc = 0;
+  bool fresh = false;
+  if (!D.d_psn_planes) {
+    rc |= h->dalloc(&D.d_psn_planes, (size_t)PSN_NF * h->Bp, true), rc |= h->dalloc(&D.d_psn_rm, (size_t)PSN_NF * h->B);
+    fresh = true;
+  }
+  if (loop && !D.d_loop_Sx) {
+    rc |= h->dalloc(&D.d_loop_Sx, (size_t)8 * LOOP_NQ * h->Bp), rc |= h->dalloc(&D.d_loop_Du, (size_t)2 * LOOP_NQ * h->Bp);
+    rc |= h->dalloc(&D.d_loop_ok, h->Bp), rc |= h->dalloc(&D.d_loop_ticks, h->Bp);
+    fresh = true;
+  }
+  if (rc) return -1;
+  if (fresh) HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// The plant-step sensitivities at (x_dev, u_dev) into the planes, with the rows in effect (those set last, as the plant step).
+int psn_launch(ltompc_solver* h, const double* x_dev, const double* u_dev, const int n_sub, const bool theta) {
+  const dim3 grid((h->B + 7) / 8), block(64);
+  if (h->pi_pend)
+    hipLaunchKernelGGL(k_plant_sens_pi, grid, block, 0, h->stream, h->K, (const double*)h->d_th_pend, h->B, h->Bp, x_dev, u_dev, h->K.o.t_step,
+                       n_sub, theta ? 1 : 0, h->dv.d_psn_planes);
+  else
+    hipLaunchKernelGGL(k_plant_sens, grid, block, 0, h->stream, h->K, h->B, h->Bp, x_dev, u_dev, h->K.o.t_step, n_sub, theta ? 1 : 0,
+                       h->dv.d_psn_planes);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// planes [f0 .. f0 + F)[Bp] -> row-major B x F at out_dev
+int planes_to_rows(ltompc_solver* h, const double* planes, const int f0, const int F, double* out_dev) {
+  const size_t n = (size_t)h->B * F;
+  hipLaunchKernelGGL(k_planes_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, planes, f0, F, h->B, h->Bp, out_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, double* dU_dp, int* ok, double* margin) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (sens_compute(h, dX_dp || dU_dp, "ltompc_get_sensitivities")) return -1;
+  const DerivState& D = h->dv;
+  const size_t B = h->B, N = h->N;
+  if (copy_out(h, D2H, du0_dp, D.d_sens_du0, 2 * SENS_NP * B) || copy_out(h, D2H, ok, D.d_sens_ok, B) ||
+      copy_out(h, D2H, margin, D.d_sens_margin, B) || copy_out(h, D2H, dX_dp, D.d_sens_dX, (N + 1) * 8 * SENS_NP * B) ||
+      copy_out(h, D2H, dU_dp, D.d_sens_dU, N * 2 * SENS_NP * B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (sens_compute(h, false, "ltompc_sensitivities_dev")) return -1;
+  if (copy_out(h, D2D, du0_dp_dev, h->dv.d_sens_du0, (size_t)2 * SENS_NP * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psens_compute(h, dX_dth || dU_dth, "ltompc_get_param_sensitivities")) return -1;
+  const DerivState& D = h->dv;
+  const size_t B = h->B, N = h->N;
+  if (copy_out(h, D2H, du0_dth, D.d_psens_du0, 2 * PS_NT * B) || copy_out(h, D2H, ok, D.d_sens_ok, B) ||
+      copy_out(h, D2H, dX_dth, D.d_psens_dX, (N + 1) * 8 * PS_NT * B) || copy_out(h, D2H, dU_dth, D.d_psens_dU, N * 2 * PS_NT * B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psens_compute(h, false, "ltompc_param_sensitivities_dev")) return -1;
+  if (copy_out(h, D2D, du0_dth_dev, h->dv.d_psens_du0, (size_t)2 * PS_NT * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_p_dev, double* grad_theta_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (adj_compute(h, gX_dev, gU_dev, grad_theta_dev != nullptr, "ltompc_adjoint_dev")) return -1;
+  if (copy_out(h, D2D, grad_p_dev, h->dv.d_adj_gp, (size_t)ADJ_NP * h->B)) return -1;
+  if (copy_out(h, D2D, grad_theta_dev, h->dv.d_adj_gth, (size_t)PS_NT * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, double* grad_p, double* grad_theta, int* ok) {
+  const char* who = "ltompc_get_adjoint";
+  if (!h) return fail("null handle");
+  if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  const size_t B = h->B, N = h->N;
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; gX && e < (N + 1) * 8; e++) fin = fin && std::isfinite(gX[b * (N + 1) * 8 + e]);
+    for (size_t e = 0; gU && e < N * 2; e++) fin = fin && std::isfinite(gU[b * N * 2 + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite cotangent of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  DerivState& D = h->dv;
+  if (gX && !D.d_adj_gX && h->dalloc(&D.d_adj_gX, (N + 1) * 8 * B)) return -1;
+  if (gU && !D.d_adj_gU && h->dalloc(&D.d_adj_gU, N * 2 * B)) return -1;
+  if (gX) HIPCHECK(hipMemcpyAsync(D.d_adj_gX, gX, sizeof(double) * (N + 1) * 8 * B, hipMemcpyHostToDevice, h->stream));
+  if (gU) HIPCHECK(hipMemcpyAsync(D.d_adj_gU, gU, sizeof(double) * N * 2 * B, hipMemcpyHostToDevice, h->stream));
+  if (adj_compute(h, gX ? D.d_adj_gX : nullptr, gU ? D.d_adj_gU : nullptr, grad_theta != nullptr, who)) return -1;
+  if (copy_out(h, D2H, grad_p, D.d_adj_gp, ADJ_NP * B) || copy_out(h, D2H, grad_theta, D.d_adj_gth, PS_NT * B) ||
+      copy_out(h, D2H, ok, D.d_sens_ok, B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_plant_sensitivities_dev(ltompc_handle h, const double* x_dev, const double* u_dev, int n_sub, double* x_next_dev, double* dxn_dx_dev,
+                                   double* dxn_du_dev, double* dxn_dtheta_dev) {
+  const char* who = "ltompc_plant_sensitivities";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x_dev || !u_dev) return fail(std::string(who) + ": null argument");
+  if (dxn_dtheta_dev && h->K.p.ptv != 0.0) return fail(std::string(who) + ": dxn_dtheta is not available with torque vectoring (ptv != 0)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psn_prepare(h, false)) return -1;
+  if (dxn_dx_dev || dxn_du_dev || dxn_dtheta_dev) {
+    const double* planes = h->dv.d_psn_planes;
+    if (psn_launch(h, x_dev, u_dev, n_sub, dxn_dtheta_dev != nullptr)) return -1;
+    if (dxn_dx_dev && planes_to_rows(h, planes, PSN_DX, 64, dxn_dx_dev)) return -1;
+    if (dxn_du_dev && planes_to_rows(h, planes, PSN_DU, 16, dxn_du_dev)) return -1;
+    if (dxn_dtheta_dev && planes_to_rows(h, planes, PSN_DTH, 8 * PS_NT, dxn_dtheta_dev)) return -1;
+  }
+  if (x_next_dev) return ltompc_plant_step_dev(h, x_dev, u_dev, n_sub, x_next_dev);  // (k_plant itself: the plant's bits)
+  return 0;
+}
+
+int ltompc_plant_sensitivities(ltompc_handle h, const double* x, const double* u, int n_sub, double* x_next, double* dxn_dx, double* dxn_du,
+                               double* dxn_dtheta) {
+  const char* who = "ltompc_plant_sensitivities";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x || !u) return fail(std::string(who) + ": null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psn_prepare(h, false)) return -1;
+  const size_t B = h->B;
+  double *rx = h->dv.d_psn_rm, *ru = rx + 64 * B, *rt = ru + 16 * B;
+  return via_io(h, x, u, x_next, [&](double* dx, double* du, double* dn) {
+    if (ltompc_plant_sensitivities_dev(h, dx, du, n_sub, dn, dxn_dx ? rx : nullptr, dxn_du ? ru : nullptr, dxn_dtheta ? rt : nullptr)) return -1;
+    return copy_out(h, D2H, dxn_dx, rx, 64 * B) || copy_out(h, D2H, dxn_du, ru, 16 * B) || copy_out(h, D2H, dxn_dtheta, rt, 8 * PS_NT * B) ? -1 : 0;
+  });
+}
+
+int ltompc_loop_begin(ltompc_handle h, int mode) {
+  const char* who = "ltompc_loop_begin";
+  if (!h) return fail("null handle");
+  if (mode < 1 || mode > 3) return fail(std::string(who) + ": mode must be 1 (theta enters the controller), 2 (the plant) or 3 (both)");
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (psn_prepare(h, true)) return -1;
+  DerivState& D = h->dv;
+  hipLaunchKernelGGL(k_loop_begin, dim3((LOOP_NQ * h->Bp + 255) / 256), dim3(256), 0, h->stream, h->B, h->Bp, D.d_loop_Sx, D.d_loop_Du,
+                     D.d_loop_ok, D.d_loop_ticks);
+  HIPCHECK(hipGetLastError());
+  D.loop_mode = mode;
+  return 0;
+}
+
+int ltompc_loop_tick_dev(ltompc_handle h, const double* x_dev, const double* u0_dev, int n_sub, double* x_next_dev) {
+  const char* who = "ltompc_loop_tick";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x_dev || !u0_dev || !x_next_dev) return fail(std::string(who) + ": null argument");
+  DerivState& D = h->dv;
+  if (!D.loop_mode) return fail(std::string(who) + ": no loop (ltompc_loop_begin first)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (sens_compute(h, false, who)) return -1;  // (the usage error after set_initial_guess comes from here)
+  if (!D.kept_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");
+  if (!D.loop_fresh) return fail(std::string(who) + ": no new solve since the last tick (make_step or make_step_dev first)");
+  const int mode = D.loop_mode;
+  if ((mode & 1) && psens_compute(h, false, who)) return -1;
+  if (psn_launch(h, x_dev, u0_dev, n_sub, (mode & 2) != 0)) return -1;
+  hipLaunchKernelGGL(k_loop_accum, dim3((LOOP_NQ * h->Bp + 255) / 256), dim3(256), 0, h->stream, h->B, h->Bp, mode, (const double*)D.d_sens_du0,
+                     (const double*)((mode & 1) ? D.d_psens_du0 : nullptr), (const int*)D.d_sens_ok, (const double*)D.d_psn_planes, D.d_loop_Sx,
+                     D.d_loop_Du, D.d_loop_ok, D.d_loop_ticks);
+  HIPCHECK(hipGetLastError());
+  D.ticked();
+  return ltompc_plant_step_dev(h, x_dev, u0_dev, n_sub, x_next_dev);
+}
+
+int ltompc_loop_tick(ltompc_handle h, const double* x, const double* u0, int n_sub, double* x_next) {
+  const char* who = "ltompc_loop_tick";
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  if (!h || !x || !u0 || !x_next) return fail(std::string(who) + ": null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  return via_io(h, x, u0, x_next, [&](double* dx, double* du, double* dn) { return ltompc_loop_tick_dev(h, dx, du, n_sub, dn); });
+}
+
+int ltompc_get_loop_sensitivities(ltompc_handle h, double* dx_dq, double* du_dq, int* ok, int* ticks) {
+  if (!h) return fail("null handle");
+  const DerivState& D = h->dv;
+  if (!D.d_loop_Sx) return fail("ltompc_get_loop_sensitivities: no loop (ltompc_loop_begin first)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (copy_out(h, D2H, ok, D.d_loop_ok, h->B) || copy_out(h, D2H, ticks, D.d_loop_ticks, h->B)) return -1;
+  if (planes_to_host(h, D.d_loop_Sx, 8 * LOOP_NQ, 1, dx_dq)) return -1;
+  if (planes_to_host(h, D.d_loop_Du, 2 * LOOP_NQ, 1, du_dq)) return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_loop_sensitivities_dev(ltompc_handle h, double* dx_dq_dev, double* du_dq_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  const DerivState& D = h->dv;
+  if (!D.d_loop_Sx) return fail("ltompc_loop_sensitivities_dev: no loop (ltompc_loop_begin first)");
+  HIPCHECK(hipSetDevice(h->device));
+  if (dx_dq_dev && planes_to_rows(h, D.d_loop_Sx, 0, 8 * LOOP_NQ, dx_dq_dev)) return -1;
+  if (du_dq_dev && planes_to_rows(h, D.d_loop_Du, 0, 2 * LOOP_NQ, du_dq_dev)) return -1;
+  return copy_out(h, D2D, ok_dev, D.d_loop_ok, h->B);
+}
+
+int ltompc_loop_end(ltompc_handle h) {
+  if (!h) return fail("null handle");
+  h->dv.loop_mode = 0;
+  return 0;
+}
+
+}  // extern "C"

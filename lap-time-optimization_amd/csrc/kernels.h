@@ -30,6 +30,7 @@
 //   plant_sensitivity.h k_plant_sens: the derivative of k_plant's discrete RK4 map w.r.t. (x, u, theta) (ltompc_plant_sensitivities);
 //                 k_loop_accum: the closed-loop recursion that chains it with the du0 outputs of the two forward passes over many
 //                 ticks (ltompc_loop_*)
+//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the four headers above
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged

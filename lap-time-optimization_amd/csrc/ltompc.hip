@@ -33,6 +33,42 @@ constexpr int NKERN = 8;  // eval, riccati, expand, linesearch, pick, update, ri
 
 }  // namespace
 
+// What the derivative passes (deriv_passes.h) keep between calls: how far each has got on the last solve, and their buffers.
+// The solver reports what became of the solve through the four transitions; only the passes advance the progress.
+enum class Sens { no_solve, solved, du0, traj };  // (x0, u_prev) pass: a solve to differentiate; du0 / ok / margin computed; trajectories too
+enum class Psens { none, du0, traj };             // theta pass: what it has computed since the last solve
+struct DerivState {
+  Sens sens = Sens::no_solve;
+  Psens psens = Psens::none;
+  bool fact = false;        // Ws' stage / Riccati buffers hold the factorisation of the last solve at the instances' current slots
+  bool pv_valid = false;    // ... and d_psens_pv k_psens_cond's planes of it
+  bool kept_uprev = false;  // d_psens_uprev holds the u_prev of the last solve (a rollout does not keep it per instance)
+  bool loop_fresh = false;  // a make_step has run since the last tick of the closed loop
+  int loop_mode = 0;        // of the closed loop begun last (0: none)
+
+  // a solve starts or an initial guess overwrites the iterate: nothing to differentiate, nothing computed, nothing stored
+  void discard() { sens = Sens::no_solve, psens = Psens::none, fact = pv_valid = kept_uprev = false; }
+  // a solve has finished; kept_u: it was a make_step, which keeps each instance's u_prev
+  void solved(const bool kept_u) { sens = Sens::solved, kept_uprev = kept_u, loop_fresh = loop_fresh || kept_u; }
+  // the instances went back to the caller's order: the stored blocks are at the wrong slots, computed results stay valid
+  void moved() { fact = pv_valid = false; }
+  void ticked() { loop_fresh = false; }
+
+  // The passes' buffers, each allocated on its first request.  (x0, u_prev) pass: Ws = the solver's Work with QP, RC, RS, LS ->
+  // buffers of the pass and si -> zeros, Wspi = Ws with TH = the rows of the last solve
+  Work Ws{}, *d_Ws = nullptr;
+  WorkPI Wspi{}, *d_Wspi = nullptr;
+  int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
+  double *d_sens_du0 = nullptr, *d_sens_margin = nullptr, *d_sens_dX = nullptr, *d_sens_dU = nullptr;
+  // theta pass; d_psens_uprev (B x 2, caller's order) is allocated with the handle: W.uprev becomes u0 at the end of a make_step
+  double *d_psens_uprev = nullptr, *d_psens_pv = nullptr, *d_psens_kf = nullptr, *d_psens_du0 = nullptr, *d_psens_dX = nullptr,
+         *d_psens_dU = nullptr;
+  // adjoint pass (d_adj_gX / d_adj_gU stage the host form's cotangents), plant step (planes and their row-major staging), closed loop
+  double *d_adj_aj = nullptr, *d_adj_gp = nullptr, *d_adj_gth = nullptr, *d_adj_gX = nullptr, *d_adj_gU = nullptr;
+  double *d_psn_planes = nullptr, *d_psn_rm = nullptr, *d_loop_Sx = nullptr, *d_loop_Du = nullptr;
+  int *d_loop_ok = nullptr, *d_loop_ticks = nullptr;
+};
+
 struct ltompc_solver {
   Consts K;
   Work W;
@@ -92,35 +128,7 @@ struct ltompc_solver {
                          // beside other handles' kernels its 4-wavefront workgroups gain nothing at 64 and lose 1 % at 512, alone it is 7 % faster)
   int ric1_width = 512;  // LTOMPC_RIC1: launches of at most this many instances use the one-wavefront-per-instance sweep (0 = never)
   int last_launches = 0, last_iterations = 0;
-  // parametric sensitivities (sensitivity.h, ltompc_get_sensitivities): the pass's own buffers, allocated on the first request.
-  // sens_state: 0 no solve to differentiate, 1 a solve to differentiate, 2 du0 / ok / margin computed, 3 trajectories too
-  int sens_state = 0;
-  bool sens_fact = false;  // the pass's stage / Riccati buffers hold the factorisation of the last solve at the instances' current slots
-  // parameter sensitivities (param_sensitivity.h, ltompc_get_param_sensitivities), on the same factorisation.
-  // psens_state: 0 not computed since the last solve, 1 du0 computed, 2 trajectories too
-  int psens_state = 0;
-  // u_prev of the last make_step in the caller's order (B x 2): W.uprev becomes u0 at its end, and the r_du columns need the
-  // Delta u_0 of the solve.  Kept by every make_step (one small copy); a rollout does not keep it (psens_uprev = false).
-  double* d_psens_uprev = nullptr;
-  bool psens_uprev = false;
-  double *d_psens_pv = nullptr, *d_psens_kf = nullptr, *d_psens_du0 = nullptr, *d_psens_dX = nullptr, *d_psens_dU = nullptr;
-  // d_psens_pv holds k_psens_cond's planes of the last solve at the instances' current slots (both passes that read them run
-  // the kernel only when it does not).  Cleared whenever the factorisation is made again: a new solve, or the instances moved.
-  bool psens_pv_valid = false;
-  // adjoint pass (adjoint.h, ltompc_get_adjoint): buffers of its own, allocated on the first request; nothing is cached per
-  // cotangent.  d_adj_gX / d_adj_gU: staging of the host form's cotangents.
-  double *d_adj_aj = nullptr, *d_adj_gp = nullptr, *d_adj_gth = nullptr, *d_adj_gX = nullptr, *d_adj_gU = nullptr;
-  // plant-step and closed-loop sensitivities (plant_sensitivity.h): buffers of their own.  d_psn_planes: k_plant_sens'
-  // [PSN_NF][Bp] planes (first request of either kind), d_psn_rm: row-major staging of the host forms; the loop's Sx, Du, ok and
-  // ticks (first loop_begin).  loop_fresh: a make_step has run since the last tick.
-  double *d_psn_planes = nullptr, *d_psn_rm = nullptr, *d_loop_Sx = nullptr, *d_loop_Du = nullptr;
-  int *d_loop_ok = nullptr, *d_loop_ticks = nullptr;
-  int loop_mode = 0;
-  bool loop_active = false, loop_fresh = false;
-  Work Ws{};                // W with QP, RC, RS, LS -> the pass's buffers, si -> zeros
-  Work* d_Ws = nullptr;
-  int *d_sens_inertia = nullptr, *d_sens_ok = nullptr;
-  double *d_sens_du0 = nullptr, *d_sens_margin = nullptr, *d_sens_dX = nullptr, *d_sens_dU = nullptr;
+  DerivState dv;  // the derivative passes on the last solve (deriv_passes.h): their progress, cached factorisation and buffers
   // per-instance vehicle and cost parameters (ltompc_set_instance_params): two [LTOMPC_NTHETA][Bp] planes in the
   // caller's order, allocated on the first set.  d_th_pend: the rows in effect for the next solve and plant step (pi_pend: set);
   // d_th_solve (WorkPI::TH): those of the last solve, copied from d_th_pend when a solve starts (pi_solve: it ran the _pi kernels),
@@ -128,8 +136,8 @@ struct ltompc_solver {
   double *d_th_pend = nullptr, *d_th_solve = nullptr;
   bool pi_pend = false, pi_solve = false;
   bool pi_narrow = true;  // the narrow _pi Riccati kernels got their LDS limit (else the _pi path runs k_riccati8_pi at every width: same bits)
-  WorkPI Wpi{}, Wspi{};  // W and Ws with TH = d_th_solve (layout.h), and their device copies: the _pi kernels' Work
-  WorkPI *d_Wpi = nullptr, *d_Wspi = nullptr;
+  WorkPI Wpi{};  // W with TH = d_th_solve (layout.h), and its device copy: the _pi kernels' Work (dv.Wspi: the same of dv.Ws)
+  WorkPI* d_Wpi = nullptr;
 
   // (P may be a gptr<T>: a global-address-space pointer in the device pass of the compiler, a plain one on the host)
   // work = true: an array that the kernels fill before they read it.  LTOMPC_POISON=1 (debug) fills those with 0xFF bytes
@@ -333,159 +341,22 @@ int ensure_unpacked(ltompc_solver* h) {
                        h->K.bd.ni, h->K.bd.nel, pass);
   HIPCHECK(hipGetLastError());
   h->packed = false;
-  h->sens_fact = false;  // (the sensitivity blocks are no longer at the instances' slots)
+  h->dv.moved();
   return 0;
 }
 
-int sync_pi_work(ltompc_solver* h);
-
-// The re-linearisation and head-less sweep of the sensitivity passes (sensitivity.h), shared by both: run once per solve, and
-// again only when the instances have moved since (same blocks, same bits, at their new slots).
-void sens_factorise(ltompc_solver* h) {
-  if (h->sens_fact) return;
-  h->psens_pv_valid = false;  // (a new solve, or the instances have moved: k_psens_cond's planes are as stale as the blocks)
-  const int N = h->N, Bp = h->Bp;
-  const bool ell = h->K.bd.nel > 0;  // the evaluation kernels the solve used (launch_iteration)
-  if (h->pi_solve) {  // (at each instance's rows of that solve, TH)
-    if (h->eval8) hipLaunchKernelGGL(k_sens_eval8_pi, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const WorkPI*)h->d_Wspi);
-    else
-      hipLaunchKernelGGL(h->ref_eval ? k_sens_eval_pi<BoundsRef> : k_sens_eval_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
-                         (const Consts*)h->d_K, (const WorkPI*)h->d_Wspi);
-    hipLaunchKernelGGL(k_sens_riccati8_pi, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, h->Wspi, (const int*)h->W.si, h->d_sens_inertia);
-    h->sens_fact = true;
-    return;
+// si and, when asked for, st of every instance on the host, in the caller's order: un-packs, copies the whole plane sets, waits
+int fetch_status(ltompc_solver* h, std::vector<int>& si, std::vector<double>* st) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (ensure_unpacked(h)) return -1;
+  si.resize((size_t)SI_NF * h->Bp);
+  HIPCHECK(hipMemcpyAsync(si.data(), h->W.si, si.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (st) {
+    st->resize((size_t)ST_NF * h->Bp);
+    HIPCHECK(hipMemcpyAsync(st->data(), h->W.st, st->size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
-  if (h->eval8) hipLaunchKernelGGL(k_sens_eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
-  else
-    hipLaunchKernelGGL(ell ? (h->ref_eval ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
-                           : (h->ref_eval ? k_sens_eval<BoundsRef, false> : k_sens_eval<BoundsAny, false>),
-                       dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, (const Consts*)h->d_K, (const Work*)h->d_Ws);
-  hipLaunchKernelGGL(k_sens_riccati8, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, h->Ws, (const int*)h->W.si, h->d_sens_inertia);
-  h->sens_fact = true;
-}
-
-// The sensitivity pass of the last solve (sensitivity.h), enqueued on the handle's stream: linearisation and head-less sweep
-// when not done since that solve (or when the instances have moved since), the forward pass for du0 / ok / margin, and the
-// trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
-int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
-  if (h->sens_state == 0) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess discards the last solve)");
-  const int B = h->B, N = h->N, Bp = h->Bp;
-  if (!h->d_Ws) {
-    Work& Ws = h->Ws;
-    Ws = h->W;
-    int rc = 0;
-    rc |= h->dalloc(&Ws.QP, (size_t)QP_NF * (N + 1) * Bp, true), rc |= h->dalloc(&Ws.RC, (size_t)RC_NF * (N + 1) * Bp, true);
-    rc |= h->dalloc(&Ws.RS, (size_t)RS_NF * N * Bp, true), rc |= h->dalloc(&Ws.LS, (size_t)3 * N * Bp, true);
-    rc |= h->dalloc(&Ws.si, (size_t)SI_NF * Bp);  // zeros, never written
-    rc |= h->dalloc(&h->d_sens_inertia, Bp), rc |= h->dalloc(&h->d_sens_ok, Bp);
-    rc |= h->dalloc(&h->d_sens_du0, (size_t)2 * SENS_NP * B), rc |= h->dalloc(&h->d_sens_margin, B);
-    rc |= h->dalloc(&h->d_Ws, 1);
-    if (rc) return -1;
-    HIPCHECK(hipMemcpyAsync(h->d_Ws, &h->Ws, sizeof(Work), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    if (h->d_th_solve && sync_pi_work(h)) return -1;
-  }
-  if (h->sens_state == 1) {
-    sens_factorise(h);
-    hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, (const int*)h->d_sens_inertia, h->K.bd.ni, h->d_sens_du0,
-                       h->d_sens_ok, h->d_sens_margin, (double*)nullptr, (double*)nullptr, (const int*)nullptr);
-    h->sens_state = 2;
-  }
-  if (traj && h->sens_state == 2) {
-    if (!h->d_sens_dX) {
-      int rc = h->dalloc(&h->d_sens_dX, (size_t)(N + 1) * 8 * SENS_NP * B);
-      rc |= h->dalloc(&h->d_sens_dU, (size_t)N * 2 * SENS_NP * B);
-      if (rc) return -1;
-    }
-    sens_factorise(h);
-    hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, (const int*)h->d_sens_inertia, h->K.bd.ni, (double*)nullptr,
-                       (int*)nullptr, (double*)nullptr, h->d_sens_dX, h->d_sens_dU, (const int*)h->d_sens_ok);
-    h->sens_state = 3;
-  }
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// What both passes over theta need: a problem that theta covers, a solve to differentiate whose u_prev was kept, the PV buffers.
-int psens_prepare(ltompc_solver* h, const char* who) {
-  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
-  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
-  if (sens_compute(h, false, who)) return -1;  // (the usage error before a solve comes from here)
-  if (!h->psens_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");
-  const int B = h->B, N = h->N, Bp = h->Bp;
-  if (!h->d_psens_pv) {
-    int rc = h->dalloc(&h->d_psens_pv, (size_t)PV_NF * N * Bp, true);
-    rc |= h->dalloc(&h->d_psens_kf, (size_t)N * 2 * PS_NT * Bp, true);
-    rc |= h->dalloc(&h->d_psens_du0, (size_t)2 * PS_NT * B);
-    if (rc) return -1;
-  }
-  return 0;
-}
-
-// The factorisation and k_psens_cond's PV planes at the instances' current slots, each only when not there already.
-void psens_condense(ltompc_solver* h) {
-  sens_factorise(h);
-  if (h->psens_pv_valid) return;
-  const int N = h->N, Bp = h->Bp;
-  if (h->pi_solve)
-    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond_pi<BoundsRef> : k_psens_cond_pi<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
-                       (const Consts*)h->d_K, (const WorkPI*)h->d_Wpi, h->d_psens_pv);
-  else
-    hipLaunchKernelGGL(h->ref_eval ? k_psens_cond<BoundsRef> : k_psens_cond<BoundsAny>, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream,
-                       (const Consts*)h->d_K, (const Work*)h->d_W, h->d_psens_pv);
-  h->psens_pv_valid = true;
-}
-
-// The parameter-sensitivity pass of the last solve (param_sensitivity.h): ok (and du0 / margin) of the pass above, whose
-// factorisation it shares, then the condensed right-hand sides of the 16 columns and their recursion.  Cached like the above.
-int psens_compute(ltompc_solver* h, const bool traj, const char* who) {
-  if (psens_prepare(h, who)) return -1;
-  const int B = h->B, N = h->N, Bp = h->Bp;
-  if (traj && !h->d_psens_dX) {
-    int rc = h->dalloc(&h->d_psens_dX, (size_t)(N + 1) * 8 * PS_NT * B);
-    rc |= h->dalloc(&h->d_psens_dU, (size_t)N * 2 * PS_NT * B);
-    if (rc) return -1;
-  }
-  if (h->psens_state == 0 || (traj && h->psens_state == 1)) {
-    psens_condense(h);
-    if (h->pi_solve) {
-      hipLaunchKernelGGL(k_psens_sweep_pi, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Wspi, (const double*)h->d_psens_uprev,
-                         (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
-                         traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
-    } else {
-      hipLaunchKernelGGL(k_psens_sweep, dim3(Bp / 8, 2), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1],
-                         (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, h->d_psens_kf, h->d_psens_du0,
-                         traj ? h->d_psens_dX : (double*)nullptr, traj ? h->d_psens_dU : (double*)nullptr);
-    }
-    h->psens_state = traj ? 2 : 1;
-  }
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// The adjoint pass of the last solve (adjoint.h) for one cotangent (device pointers, caller's order; either may be null), into
-// d_adj_gp and, with theta, d_adj_gth: the factorisation and the PV planes when not there, then one sweep.  Once its buffers
-// exist it only enqueues.
-int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, const bool theta, const char* who) {
-  if (!gX_dev && !gU_dev) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
-  if (theta ? psens_prepare(h, who) : sens_compute(h, false, who)) return -1;
-  const int B = h->B, N = h->N, Bp = h->Bp;
-  if (!h->d_adj_gp) {
-    int rc = h->dalloc(&h->d_adj_gp, (size_t)ADJ_NP * B);
-    rc |= h->dalloc(&h->d_adj_gth, (size_t)PS_NT * B);
-    if (rc) return -1;
-  }
-  if (theta && !h->d_adj_aj && h->dalloc(&h->d_adj_aj, (size_t)AJ_NF * N * Bp, true)) return -1;
-  if (theta) psens_condense(h);
-  else sens_factorise(h);
-  double* const gth = theta ? h->d_adj_gth : nullptr;
-  if (h->pi_solve)
-    hipLaunchKernelGGL(k_adj_sweep_pi, dim3(Bp / 8), dim3(64), 0, h->stream, h->Wspi, (const double*)h->d_psens_uprev, (const double*)h->d_psens_pv,
-                       (const int*)h->d_sens_ok, gX_dev, gU_dev, h->d_adj_aj, h->d_adj_gp, gth);
-  else
-    hipLaunchKernelGGL(k_adj_sweep, dim3(Bp / 8), dim3(64), 0, h->stream, h->Ws, h->K.p.r_du[0], h->K.p.r_du[1], (const double*)h->d_psens_uprev,
-                       (const double*)h->d_psens_pv, (const int*)h->d_sens_ok, gX_dev, gU_dev, h->d_adj_aj, h->d_adj_gp, gth);
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -493,9 +364,9 @@ int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, co
 int sync_pi_work(ltompc_solver* h) {
   static_cast<Work&>(h->Wpi) = h->W, h->Wpi.TH = (gptr<const double>)h->d_th_solve;
   HIPCHECK(hipMemcpyAsync(h->d_Wpi, &h->Wpi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream));
-  if (h->d_Ws) {
-    static_cast<Work&>(h->Wspi) = h->Ws, h->Wspi.TH = (gptr<const double>)h->d_th_solve;
-    HIPCHECK(hipMemcpyAsync(h->d_Wspi, &h->Wspi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream));
+  if (h->dv.d_Ws) {
+    static_cast<Work&>(h->dv.Wspi) = h->dv.Ws, h->dv.Wspi.TH = (gptr<const double>)h->d_th_solve;
+    HIPCHECK(hipMemcpyAsync(h->dv.d_Wspi, &h->dv.Wspi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream));
   }
   HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
@@ -523,7 +394,7 @@ int theta_prepare(ltompc_solver* h, const char* who) {
   if (h->dalloc(&h->d_th_pend, plane.size()) || h->dalloc(&h->d_th_solve, plane.size())) return -1;
   HIPCHECK(hipMemcpyAsync(h->d_th_pend, plane.data(), plane.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipMemcpyAsync(h->d_th_solve, plane.data(), plane.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (h->dalloc(&h->d_Wpi, 1) || h->dalloc(&h->d_Wspi, 1)) return -1;
+  if (h->dalloc(&h->d_Wpi, 1) || h->dalloc(&h->dv.d_Wspi, 1)) return -1;
   return sync_pi_work(h);
 }
 
@@ -535,47 +406,22 @@ int commit_theta(ltompc_solver* h) {
   return 0;
 }
 
-// k_plant_sens' planes and the row-major staging of the host forms and, with `loop`, the closed loop's state: each on the first
-// request, with one synchronisation.
-int psn_prepare(ltompc_solver* h, const bool loop) {
-  int rc = 0;
-  bool fresh = false;
-  if (!h->d_psn_planes) {
-    rc |= h->dalloc(&h->d_psn_planes, (size_t)PSN_NF * h->Bp, true), rc |= h->dalloc(&h->d_psn_rm, (size_t)PSN_NF * h->B);
-    fresh = true;
-  }
-  if (loop && !h->d_loop_Sx) {
-    rc |= h->dalloc(&h->d_loop_Sx, (size_t)8 * LOOP_NQ * h->Bp), rc |= h->dalloc(&h->d_loop_Du, (size_t)2 * LOOP_NQ * h->Bp);
-    rc |= h->dalloc(&h->d_loop_ok, h->Bp), rc |= h->dalloc(&h->d_loop_ticks, h->Bp);
-    fresh = true;
-  }
-  if (rc) return -1;
-  if (fresh) HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-// The plant-step sensitivities at (x_dev, u_dev) into the planes, with the rows in effect (those set last, as the plant step).
-int psn_launch(ltompc_solver* h, const double* x_dev, const double* u_dev, const int n_sub, const bool theta) {
-  const dim3 grid((h->B + 7) / 8), block(64);
-  if (h->pi_pend)
-    hipLaunchKernelGGL(k_plant_sens_pi, grid, block, 0, h->stream, h->K, (const double*)h->d_th_pend, h->B, h->Bp, x_dev, u_dev, h->K.o.t_step,
-                       n_sub, theta ? 1 : 0, h->d_psn_planes);
-  else
-    hipLaunchKernelGGL(k_plant_sens, grid, block, 0, h->stream, h->K, h->B, h->Bp, x_dev, u_dev, h->K.o.t_step, n_sub, theta ? 1 : 0,
-                       h->d_psn_planes);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// planes [f0 .. f0 + F)[Bp] -> row-major B x F at out_dev
-int planes_to_rows(ltompc_solver* h, const double* planes, const int f0, const int F, double* out_dev) {
-  const size_t n = (size_t)h->B * F;
-  hipLaunchKernelGGL(k_planes_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, planes, f0, F, h->B, h->Bp, out_dev);
-  HIPCHECK(hipGetLastError());
+// Host form of an entry point on (x, u): both through the d_io staging, `dev` on the device copies (its x_next to dn when asked
+// for), x_next back, one synchronisation
+template <typename F>
+int via_io(ltompc_solver* h, const double* x, const double* u, double* x_next, const F& dev) {
+  double *dx = h->d_io, *du = dx + 8 * (size_t)h->Bp, *dn = dx + 10 * (size_t)h->Bp;
+  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * h->B, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(du, u, sizeof(double) * 2 * h->B, hipMemcpyHostToDevice, h->stream));
+  if (dev(dx, du, x_next ? dn : nullptr)) return -1;
+  if (x_next) HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * h->B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
 }  // namespace
+
+#include "deriv_passes.h"
 
 extern "C" {
 
@@ -741,7 +587,7 @@ int ltompc_create(const ltompc_params* params, const ltompc_options* options, co
   rc |= h->dalloc(&W.QP, (size_t)QP_NF * (N + 1) * Bp, true), rc |= h->dalloc(&W.RC, (size_t)RC_NF * (N + 1) * Bp, true);
   rc |= h->dalloc(&W.RS, (size_t)RS_NF * N * Bp, true), rc |= h->dalloc(&W.SP, (size_t)SP_NF * N * Bp, true);
   rc |= h->dalloc(&W.LS, (size_t)3 * (options->n_linesearch + 1) * N * Bp, true);
-  rc |= h->dalloc(&W.x0, 8 * Bp), rc |= h->dalloc(&W.uprev, 2 * Bp), rc |= h->dalloc(&h->d_psens_uprev, 2 * Bp);
+  rc |= h->dalloc(&W.x0, 8 * Bp), rc |= h->dalloc(&W.uprev, 2 * Bp), rc |= h->dalloc(&h->dv.d_psens_uprev, 2 * Bp);
   rc |= h->dalloc(&W.st, (size_t)ST_NF * Bp), rc |= h->dalloc(&W.filt, (size_t)2 * FILTER_MAX * Bp);
   rc |= h->dalloc(&W.si, (size_t)SI_NF * Bp), rc |= h->dalloc(&W.active, (size_t)h->max_iter + 2);
   rc |= h->dalloc(&h->d_act[0], Bp), rc |= h->dalloc(&h->d_act[1], Bp), rc |= h->dalloc(&h->d_nact[0], 4), rc |= h->dalloc(&h->d_nact[1], 4);
@@ -837,7 +683,7 @@ int ltompc_set_initial_guess_dev(ltompc_handle h, const double* x0_dev) {
   if (!h || !x0_dev) return fail("ltompc_set_initial_guess: null argument");
   HIPCHECK(hipSetDevice(h->device));
   h->packed = false;  // a cold start overwrites the whole iterate: nothing to restore
-  h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;  // (nor a solve to differentiate)
+  h->dv.discard();  // (nor a solve to differentiate)
   hipLaunchKernelGGL(k_act_identity, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->d_orig, h->d_perm, h->B);  // (slot -> caller's index: identity again)
   hipLaunchKernelGGL(k_load_x0, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)nullptr, 0, 0);
   hipLaunchKernelGGL(k_zero_uprev, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -864,7 +710,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   const int B = h->B, N = h->N, Bp = h->Bp;
   const bool ell = h->K.bd.nel > 0;  // kernels instantiated with / without the friction-ellipse constraints
   Launcher L{h};
-  h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;
+  h->dv.discard();
   if (commit_theta(h)) return -1;
   hipLaunchKernelGGL(k_load_x0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)(h->packed ? h->d_orig : nullptr),
                      h->K.o.resto_sticky, h->cold_next ? 0 : 1);
@@ -944,13 +790,12 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
     }
   }
   if (L.close()) return -1;
-  hipLaunchKernelGGL(k_psens_keep_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, h->d_psens_uprev, (const int*)(h->packed ? h->d_orig : nullptr));
+  hipLaunchKernelGGL(k_psens_keep_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, h->dv.d_psens_uprev, (const int*)(h->packed ? h->d_orig : nullptr));
   hipLaunchKernelGGL(k_store_u0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, u0_dev, (const int*)(h->packed ? h->d_orig : nullptr));
   HIPCHECK(hipGetLastError());
-  h->psens_uprev = true, h->loop_fresh = true;
   h->last_launches = L.launches + 3;
   h->last_iterations = it + 1;
-  h->sens_state = 1;
+  h->dv.solved(true);
   if (h->profiling) {
     HIPCHECK(hipStreamSynchronize(h->stream));
     if (collect_profile(h)) return -1;
@@ -966,14 +811,9 @@ int ltompc_synchronize(ltompc_handle h) {
 }
 
 int ltompc_get_stats(ltompc_handle h, int* status, int* iters, double* kkt_error, double* objective, double* mu) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (ensure_unpacked(h)) return -1;
-  std::vector<int> si((size_t)SI_NF * h->Bp);
-  std::vector<double> st((size_t)ST_NF * h->Bp);
-  HIPCHECK(hipMemcpyAsync(si.data(), h->W.si, si.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipMemcpyAsync(st.data(), h->W.st, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  std::vector<int> si;
+  std::vector<double> st;
+  if (fetch_status(h, si, &st)) return -1;
   for (int b = 0; b < h->B; b++) {
     if (status) status[b] = si[(size_t)SI_STATUS * h->Bp + b];
     if (iters) iters[b] = si[(size_t)SI_ITERS * h->Bp + b];
@@ -985,12 +825,8 @@ int ltompc_get_stats(ltompc_handle h, int* status, int* iters, double* kkt_error
 }
 
 int ltompc_get_counters(ltompc_handle h, int* n_reg, int* n_lsfail) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (ensure_unpacked(h)) return -1;
-  std::vector<int> si((size_t)SI_NF * h->Bp);
-  HIPCHECK(hipMemcpyAsync(si.data(), h->W.si, si.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  std::vector<int> si;
+  if (fetch_status(h, si, nullptr)) return -1;
   for (int b = 0; b < h->B; b++) {
     if (n_reg) n_reg[b] = si[(size_t)SI_NREG * h->Bp + b];
     if (n_lsfail) n_lsfail[b] = si[(size_t)SI_NLSFAIL * h->Bp + b];
@@ -999,14 +835,9 @@ int ltompc_get_counters(ltompc_handle h, int* n_reg, int* n_lsfail) {
 }
 
 int ltompc_get_restoration(ltompc_handle h, int* n_resto, double* violation) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (ensure_unpacked(h)) return -1;
-  std::vector<int> si((size_t)SI_NF * h->Bp);
-  std::vector<double> st((size_t)ST_NF * h->Bp);
-  HIPCHECK(hipMemcpyAsync(si.data(), h->W.si, si.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipMemcpyAsync(st.data(), h->W.st, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  std::vector<int> si;
+  std::vector<double> st;
+  if (fetch_status(h, si, &st)) return -1;
   for (int b = 0; b < h->B; b++) {
     if (n_resto) n_resto[b] = si[(size_t)SI_NRESTO * h->Bp + b];
     // (meaningful while the elastic variables exist: 0 once the solve is back on the hard constraints; g(x0) when the
@@ -1018,14 +849,9 @@ int ltompc_get_restoration(ltompc_handle h, int* n_resto, double* violation) {
 }
 
 int ltompc_get_recovery(ltompc_handle h, int* n_shift, int* n_fallback, double* g0, int* solver_status, double* penalty) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (ensure_unpacked(h)) return -1;
-  std::vector<int> si((size_t)SI_NF * h->Bp);
-  std::vector<double> st((size_t)ST_NF * h->Bp);
-  HIPCHECK(hipMemcpyAsync(si.data(), h->W.si, si.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipMemcpyAsync(st.data(), h->W.st, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  std::vector<int> si;
+  std::vector<double> st;
+  if (fetch_status(h, si, &st)) return -1;
   for (int b = 0; b < h->B; b++) {
     if (n_shift) n_shift[b] = si[(size_t)SI_NSHIFT * h->Bp + b];
     if (n_fallback) n_fallback[b] = si[(size_t)SI_NFALLBACK * h->Bp + b];
@@ -1045,7 +871,7 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   if (h->eval8) return fail("ltompc_rollout: latency-mode handles (8-lanes-per-slot kernels) are not supported by the rollout");
   HIPCHECK(hipSetDevice(h->device));
   if (ensure_unpacked(h)) return -1;  // the rollout works in the caller's order (index-list compaction only)
-  h->sens_state = 0, h->psens_state = 0, h->sens_fact = false;
+  h->dv.discard();
   if (commit_theta(h)) return -1;
   constexpr int RING = ltompc_solver::ROLL_RING;
   if (!h->plant_streams[0]) {
@@ -1159,91 +985,8 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   h->roll_iterations = it + 1, h->roll_launches = L.launches;
   h->last_iterations = 0;  // (no per-iteration history after a rollout: ltompc_get_active_history returns 0)
   h->after_rollout = true;
-  h->psens_uprev = false;
-  if (rc == 0) h->sens_state = 1;
+  if (rc == 0) h->dv.solved(false);
   return rc;
-}
-
-int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, double* dU_dp, int* ok, double* margin) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (sens_compute(h, dX_dp || dU_dp, "ltompc_get_sensitivities")) return -1;
-  const size_t B = h->B, N = h->N;
-  if (du0_dp) HIPCHECK(hipMemcpyAsync(du0_dp, h->d_sens_du0, sizeof(double) * 2 * SENS_NP * B, hipMemcpyDeviceToHost, h->stream));
-  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-  if (margin) HIPCHECK(hipMemcpyAsync(margin, h->d_sens_margin, sizeof(double) * B, hipMemcpyDeviceToHost, h->stream));
-  if (dX_dp) HIPCHECK(hipMemcpyAsync(dX_dp, h->d_sens_dX, sizeof(double) * (N + 1) * 8 * SENS_NP * B, hipMemcpyDeviceToHost, h->stream));
-  if (dU_dp) HIPCHECK(hipMemcpyAsync(dU_dp, h->d_sens_dU, sizeof(double) * N * 2 * SENS_NP * B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (sens_compute(h, false, "ltompc_sensitivities_dev")) return -1;
-  const size_t B = h->B;
-  if (du0_dp_dev) HIPCHECK(hipMemcpyAsync(du0_dp_dev, h->d_sens_du0, sizeof(double) * 2 * SENS_NP * B, hipMemcpyDeviceToDevice, h->stream));
-  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
-  return 0;
-}
-
-int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (psens_compute(h, dX_dth || dU_dth, "ltompc_get_param_sensitivities")) return -1;
-  const size_t B = h->B, N = h->N;
-  if (du0_dth) HIPCHECK(hipMemcpyAsync(du0_dth, h->d_psens_du0, sizeof(double) * 2 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
-  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-  if (dX_dth) HIPCHECK(hipMemcpyAsync(dX_dth, h->d_psens_dX, sizeof(double) * (N + 1) * 8 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
-  if (dU_dth) HIPCHECK(hipMemcpyAsync(dU_dth, h->d_psens_dU, sizeof(double) * N * 2 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (psens_compute(h, false, "ltompc_param_sensitivities_dev")) return -1;
-  const size_t B = h->B;
-  if (du0_dth_dev) HIPCHECK(hipMemcpyAsync(du0_dth_dev, h->d_psens_du0, sizeof(double) * 2 * PS_NT * B, hipMemcpyDeviceToDevice, h->stream));
-  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
-  return 0;
-}
-
-int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_p_dev, double* grad_theta_dev, int* ok_dev) {
-  if (!h) return fail("null handle");
-  HIPCHECK(hipSetDevice(h->device));
-  if (adj_compute(h, gX_dev, gU_dev, grad_theta_dev != nullptr, "ltompc_adjoint_dev")) return -1;
-  const size_t B = h->B;
-  if (grad_p_dev) HIPCHECK(hipMemcpyAsync(grad_p_dev, h->d_adj_gp, sizeof(double) * ADJ_NP * B, hipMemcpyDeviceToDevice, h->stream));
-  if (grad_theta_dev) HIPCHECK(hipMemcpyAsync(grad_theta_dev, h->d_adj_gth, sizeof(double) * PS_NT * B, hipMemcpyDeviceToDevice, h->stream));
-  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToDevice, h->stream));
-  return 0;
-}
-
-int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, double* grad_p, double* grad_theta, int* ok) {
-  const char* who = "ltompc_get_adjoint";
-  if (!h) return fail("null handle");
-  if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
-  const size_t B = h->B, N = h->N;
-  for (size_t b = 0; b < B; b++) {
-    bool fin = true;
-    for (size_t e = 0; gX && e < (N + 1) * 8; e++) fin = fin && std::isfinite(gX[b * (N + 1) * 8 + e]);
-    for (size_t e = 0; gU && e < N * 2; e++) fin = fin && std::isfinite(gU[b * N * 2 + e]);
-    if (!fin) return fail(std::string(who) + ": non-finite cotangent of instance " + std::to_string(b));
-  }
-  HIPCHECK(hipSetDevice(h->device));
-  if (gX && !h->d_adj_gX && h->dalloc(&h->d_adj_gX, (N + 1) * 8 * B)) return -1;
-  if (gU && !h->d_adj_gU && h->dalloc(&h->d_adj_gU, N * 2 * B)) return -1;
-  if (gX) HIPCHECK(hipMemcpyAsync(h->d_adj_gX, gX, sizeof(double) * (N + 1) * 8 * B, hipMemcpyHostToDevice, h->stream));
-  if (gU) HIPCHECK(hipMemcpyAsync(h->d_adj_gU, gU, sizeof(double) * N * 2 * B, hipMemcpyHostToDevice, h->stream));
-  if (adj_compute(h, gX ? h->d_adj_gX : nullptr, gU ? h->d_adj_gU : nullptr, grad_theta != nullptr, who)) return -1;
-  if (grad_p) HIPCHECK(hipMemcpyAsync(grad_p, h->d_adj_gp, sizeof(double) * ADJ_NP * B, hipMemcpyDeviceToHost, h->stream));
-  if (grad_theta) HIPCHECK(hipMemcpyAsync(grad_theta, h->d_adj_gth, sizeof(double) * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
-  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_sens_ok, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
 }
 
 int ltompc_get_prediction_dev(ltompc_handle h, double* X_dev, double* U_dev) {
@@ -1372,133 +1115,7 @@ int ltompc_plant_step_dev(ltompc_handle h, const double* x_dev, const double* u_
 int ltompc_plant_step(ltompc_handle h, const double* x, const double* u, int n_sub, double* x_next) {
   if (!h || !x || !u || !x_next) return fail("ltompc_plant_step: null argument");
   HIPCHECK(hipSetDevice(h->device));
-  double *dx = h->d_io, *du = h->d_io + 8 * (size_t)h->Bp, *dn = h->d_io + 10 * (size_t)h->Bp;
-  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * h->B, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(du, u, sizeof(double) * 2 * h->B, hipMemcpyHostToDevice, h->stream));
-  int rc = ltompc_plant_step_dev(h, dx, du, n_sub, dn);
-  if (rc) return rc;
-  HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * h->B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int ltompc_plant_sensitivities_dev(ltompc_handle h, const double* x_dev, const double* u_dev, int n_sub, double* x_next_dev, double* dxn_dx_dev,
-                                   double* dxn_du_dev, double* dxn_dtheta_dev) {
-  const char* who = "ltompc_plant_sensitivities";
-  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
-  if (!h || !x_dev || !u_dev) return fail(std::string(who) + ": null argument");
-  if (dxn_dtheta_dev && h->K.p.ptv != 0.0) return fail(std::string(who) + ": dxn_dtheta is not available with torque vectoring (ptv != 0)");
-  HIPCHECK(hipSetDevice(h->device));
-  if (psn_prepare(h, false)) return -1;
-  if (dxn_dx_dev || dxn_du_dev || dxn_dtheta_dev) {
-    if (psn_launch(h, x_dev, u_dev, n_sub, dxn_dtheta_dev != nullptr)) return -1;
-    if (dxn_dx_dev && planes_to_rows(h, h->d_psn_planes, PSN_DX, 64, dxn_dx_dev)) return -1;
-    if (dxn_du_dev && planes_to_rows(h, h->d_psn_planes, PSN_DU, 16, dxn_du_dev)) return -1;
-    if (dxn_dtheta_dev && planes_to_rows(h, h->d_psn_planes, PSN_DTH, 8 * PS_NT, dxn_dtheta_dev)) return -1;
-  }
-  if (x_next_dev) return ltompc_plant_step_dev(h, x_dev, u_dev, n_sub, x_next_dev);  // (k_plant itself: the plant's bits)
-  return 0;
-}
-
-int ltompc_plant_sensitivities(ltompc_handle h, const double* x, const double* u, int n_sub, double* x_next, double* dxn_dx, double* dxn_du,
-                               double* dxn_dtheta) {
-  const char* who = "ltompc_plant_sensitivities";
-  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
-  if (!h || !x || !u) return fail(std::string(who) + ": null argument");
-  HIPCHECK(hipSetDevice(h->device));
-  if (psn_prepare(h, false)) return -1;
-  const size_t B = h->B;
-  double *dx = h->d_io, *du = h->d_io + 8 * (size_t)h->Bp, *dn = h->d_io + 10 * (size_t)h->Bp;
-  double *rx = h->d_psn_rm, *ru = rx + 64 * B, *rt = ru + 16 * B;
-  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * B, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(du, u, sizeof(double) * 2 * B, hipMemcpyHostToDevice, h->stream));
-  if (ltompc_plant_sensitivities_dev(h, dx, du, n_sub, x_next ? dn : nullptr, dxn_dx ? rx : nullptr, dxn_du ? ru : nullptr,
-                                     dxn_dtheta ? rt : nullptr))
-    return -1;
-  if (x_next) HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * B, hipMemcpyDeviceToHost, h->stream));
-  if (dxn_dx) HIPCHECK(hipMemcpyAsync(dxn_dx, rx, sizeof(double) * 64 * B, hipMemcpyDeviceToHost, h->stream));
-  if (dxn_du) HIPCHECK(hipMemcpyAsync(dxn_du, ru, sizeof(double) * 16 * B, hipMemcpyDeviceToHost, h->stream));
-  if (dxn_dtheta) HIPCHECK(hipMemcpyAsync(dxn_dtheta, rt, sizeof(double) * 8 * PS_NT * B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int ltompc_loop_begin(ltompc_handle h, int mode) {
-  const char* who = "ltompc_loop_begin";
-  if (!h) return fail("null handle");
-  if (mode < 1 || mode > 3) return fail(std::string(who) + ": mode must be 1 (theta enters the controller), 2 (the plant) or 3 (both)");
-  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
-  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
-  HIPCHECK(hipSetDevice(h->device));
-  if (psn_prepare(h, true)) return -1;
-  const int B = h->B, Bp = h->Bp;
-  hipLaunchKernelGGL(k_loop_begin, dim3((LOOP_NQ * Bp + 255) / 256), dim3(256), 0, h->stream, B, Bp, h->d_loop_Sx, h->d_loop_Du, h->d_loop_ok,
-                     h->d_loop_ticks);
-  HIPCHECK(hipGetLastError());
-  h->loop_mode = mode, h->loop_active = true;
-  return 0;
-}
-
-int ltompc_loop_tick_dev(ltompc_handle h, const double* x_dev, const double* u0_dev, int n_sub, double* x_next_dev) {
-  const char* who = "ltompc_loop_tick";
-  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
-  if (!h || !x_dev || !u0_dev || !x_next_dev) return fail(std::string(who) + ": null argument");
-  if (!h->loop_active) return fail(std::string(who) + ": no loop (ltompc_loop_begin first)");
-  HIPCHECK(hipSetDevice(h->device));
-  if (sens_compute(h, false, who)) return -1;  // (the usage error after set_initial_guess comes from here)
-  if (!h->psens_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");
-  if (!h->loop_fresh) return fail(std::string(who) + ": no new solve since the last tick (make_step or make_step_dev first)");
-  const int mode = h->loop_mode;
-  if ((mode & 1) && psens_compute(h, false, who)) return -1;
-  if (psn_launch(h, x_dev, u0_dev, n_sub, (mode & 2) != 0)) return -1;
-  hipLaunchKernelGGL(k_loop_accum, dim3((LOOP_NQ * h->Bp + 255) / 256), dim3(256), 0, h->stream, h->B, h->Bp, mode, (const double*)h->d_sens_du0,
-                     (const double*)((mode & 1) ? h->d_psens_du0 : nullptr), (const int*)h->d_sens_ok, (const double*)h->d_psn_planes, h->d_loop_Sx,
-                     h->d_loop_Du, h->d_loop_ok, h->d_loop_ticks);
-  HIPCHECK(hipGetLastError());
-  h->loop_fresh = false;
-  return ltompc_plant_step_dev(h, x_dev, u0_dev, n_sub, x_next_dev);
-}
-
-int ltompc_loop_tick(ltompc_handle h, const double* x, const double* u0, int n_sub, double* x_next) {
-  const char* who = "ltompc_loop_tick";
-  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
-  if (!h || !x || !u0 || !x_next) return fail(std::string(who) + ": null argument");
-  HIPCHECK(hipSetDevice(h->device));
-  double *dx = h->d_io, *du = h->d_io + 8 * (size_t)h->Bp, *dn = h->d_io + 10 * (size_t)h->Bp;
-  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * h->B, hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(du, u0, sizeof(double) * 2 * h->B, hipMemcpyHostToDevice, h->stream));
-  if (ltompc_loop_tick_dev(h, dx, du, n_sub, dn)) return -1;
-  HIPCHECK(hipMemcpyAsync(x_next, dn, sizeof(double) * 8 * h->B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int ltompc_get_loop_sensitivities(ltompc_handle h, double* dx_dq, double* du_dq, int* ok, int* ticks) {
-  if (!h) return fail("null handle");
-  if (!h->d_loop_Sx) return fail("ltompc_get_loop_sensitivities: no loop (ltompc_loop_begin first)");
-  HIPCHECK(hipSetDevice(h->device));
-  if (ok) HIPCHECK(hipMemcpyAsync(ok, h->d_loop_ok, sizeof(int) * h->B, hipMemcpyDeviceToHost, h->stream));
-  if (ticks) HIPCHECK(hipMemcpyAsync(ticks, h->d_loop_ticks, sizeof(int) * h->B, hipMemcpyDeviceToHost, h->stream));
-  if (planes_to_host(h, h->d_loop_Sx, 8 * LOOP_NQ, 1, dx_dq)) return -1;
-  if (planes_to_host(h, h->d_loop_Du, 2 * LOOP_NQ, 1, du_dq)) return -1;
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-int ltompc_loop_sensitivities_dev(ltompc_handle h, double* dx_dq_dev, double* du_dq_dev, int* ok_dev) {
-  if (!h) return fail("null handle");
-  if (!h->d_loop_Sx) return fail("ltompc_loop_sensitivities_dev: no loop (ltompc_loop_begin first)");
-  HIPCHECK(hipSetDevice(h->device));
-  if (dx_dq_dev && planes_to_rows(h, h->d_loop_Sx, 0, 8 * LOOP_NQ, dx_dq_dev)) return -1;
-  if (du_dq_dev && planes_to_rows(h, h->d_loop_Du, 0, 2 * LOOP_NQ, du_dq_dev)) return -1;
-  if (ok_dev) HIPCHECK(hipMemcpyAsync(ok_dev, h->d_loop_ok, sizeof(int) * h->B, hipMemcpyDeviceToDevice, h->stream));
-  return 0;
-}
-
-int ltompc_loop_end(ltompc_handle h) {
-  if (!h) return fail("null handle");
-  h->loop_active = false;
-  return 0;
+  return via_io(h, x, u, x_next, [&](double* dx, double* du, double* dn) { return ltompc_plant_step_dev(h, dx, du, n_sub, dn); });
 }
 
 int ltompc_slip_forces(ltompc_handle h, const double* x, int batch, double* alpha, double* Fy) {

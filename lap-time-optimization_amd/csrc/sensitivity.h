@@ -66,9 +66,11 @@ __global__ void __launch_bounds__(64) k_sens_eval_pi(const Consts* __restrict__ 
 }
 
 // si_solve: the solver's own si planes (read only).  An instance is differentiated when the solver's status (before the
-// node-0 rule) is SOLVED or ACCEPTABLE; inertia[b] = 1 when every stage's Huu is positive definite at delta_w = 0.
-__global__ void __launch_bounds__(64) k_sens_riccati8(Consts K, Work Ws, const int* __restrict__ si_solve, int* __restrict__ inertia) {
-  __shared__ RicLds L;
+// node-0 rule) is SOLVED or ACCEPTABLE and it was not re-initialised; inertia[b] = 1 when every stage's Huu is positive definite
+// at delta_w = 0.
+template <bool PI>
+__device__ __forceinline__ void d_sens_riccati8(const Consts& K, const Work& Ws, RicLds& L, const int* __restrict__ si_solve,
+                                                int* __restrict__ inertia) {
   const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
   const int j = blockIdx.x * 8 + g;
   const bool valid = j < Ws.B;
@@ -77,19 +79,15 @@ __global__ void __launch_bounds__(64) k_sens_riccati8(Consts K, Work Ws, const i
   const int node0 = si_solve[(size_t)SI_NODE0 * Bp + b];
   const int status = node0 ? node0 - 1 : si_solve[(size_t)SI_STATUS * Bp + b];
   const bool el = valid && (status == LTOMPC_STATUS_SOLVED || status == LTOMPC_STATUS_ACCEPTABLE) && !si_solve[(size_t)SI_REINIT * Bp + b];
-  d_riccati8<true>(K, Ws, L, g, i, b, valid, -1, 1, el, inertia);
+  d_riccati8<true, PI>(K, Ws, L, g, i, b, valid, -1, 1, el, inertia);
+}
+__global__ void __launch_bounds__(64) k_sens_riccati8(Consts K, Work Ws, const int* __restrict__ si_solve, int* __restrict__ inertia) {
+  __shared__ RicLds L;
+  d_sens_riccati8<false>(K, Ws, L, si_solve, inertia);
 }
 __global__ void __launch_bounds__(64) k_sens_riccati8_pi(Consts K, WorkPI Ws, const int* __restrict__ si_solve, int* __restrict__ inertia) {
   __shared__ RicLds L;
-  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
-  const int j = blockIdx.x * 8 + g;
-  const bool valid = j < Ws.B;
-  const int b = valid ? j : 0;
-  const size_t Bp = Ws.Bp;
-  const int node0 = si_solve[(size_t)SI_NODE0 * Bp + b];
-  const int status = node0 ? node0 - 1 : si_solve[(size_t)SI_STATUS * Bp + b];
-  const bool el = valid && (status == LTOMPC_STATUS_SOLVED || status == LTOMPC_STATUS_ACCEPTABLE) && !si_solve[(size_t)SI_REINIT * Bp + b];
-  d_riccati8<true, true>(K, Ws, L, g, i, b, valid, -1, 1, el, inertia);
+  d_sens_riccati8<true>(K, Ws, L, si_solve, inertia);
 }
 
 // Forward propagation of the 10 directions.  Wave = 8 instances x 8 lanes; lane (g, i) carries row i of dX_k (10 columns),

@@ -400,7 +400,7 @@ int main(int argc, char** argv) {
     }
   };
   std::vector<double> x(x0), u0((size_t)2 * B, 0.0), xn((size_t)8 * B);
-  // k_plant_sens' planes (psn_prepare / psn_launch of ltompc.hip): a work plane set, at the rows in effect
+  // k_plant_sens' planes (psn_prepare / psn_launch of deriv_passes.h): a work plane set, at the rows in effect
   double* psn = poisoned((size_t)PSN_NF * bp);
   const auto run_plant_sens = [&](const double* xs, const double* us, const int n_sub, const int with_theta) {
     const Consts Kc = K;  // (one wavefront = 8 instances x 8 lanes that exchange nothing: no collective, lane after lane)
@@ -430,7 +430,7 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  // The derivative passes (sens_compute, sens_factorise, psens_prepare, psens_condense, psens_compute, adj_compute of ltompc.hip):
+  // The derivative passes (sens_compute, sens_factorise, psens_prepare, psens_condense, psens_compute, adj_compute of deriv_passes.h):
   // Ws = W with the pass's own QP / RC / RS / LS (work planes) and a zeroed si; PV, KF, AJ work planes; outputs zeroed as the
   // library's; Wspi = Ws + TH (sync_pi_work).
   Work Ws = W;
