@@ -405,6 +405,49 @@ int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_d
  * prediction, ltompc_adjoint_dev, the next make_step_dev) never pays for un-packing. */
 int ltompc_get_prediction_dev(ltompc_handle h, double* X_dev, double* U_dev);
 
+/* Directional sensitivities of the last solve: the product of the Jacobians of the predicted trajectory with ONE
+ * direction dp of p = (x0[0..7], u_prev[0..1]) and dtheta of theta (the LTOMPC_NTHETA = 16 columns above, natural units), without
+ * forming a Jacobian.  For instance b:
+ *     tX[k,i] = sum_{j < 10} dX_dp[k,i,j] dp[j] + sum_{j < 16} dX_dth[k,i,j] dtheta[j]
+ *     tU[k,c] = sum_{j < 10} dU_dp[k,c,j] dp[j] + sum_{j < 16} dU_dth[k,c,j] dtheta[j]
+ * with dX_dp, dU_dp, dX_dth, dU_dth exactly the outputs of ltompc_get_sensitivities and ltompc_get_param_sensitivities (same
+ * definition, same instances).  Block 0 of tX is dp[0..7] as it is; block 0 of tU is du0_dp dp + du0_dth dtheta.
+ *   ok[b] equals ltompc_get_sensitivities' ok[b] bit for bit; every output of an instance with ok[b] = 0 is exactly 0.
+ * The linearised KKT system is linear in its right-hand side: with dtheta, ONE backward recursion of the dtheta-weighted sum of
+ * the condensed right-hand sides of the 16 columns on the delta_w = 0 factorisation, then ONE forward recursion from (dp[0..7],
+ * dp[8..9]); without dtheta only the forward recursion.
+ *
+ * Inputs, in the caller's instance order:
+ *   dp  batch x 10 (x0[0..7], u_prev[0..1]);   dtheta  batch x 16.   Either may be NULL (= zeros); both NULL is a usage error.
+ * Outputs, in the caller's instance order, any may be NULL:
+ *   tX  batch x (N+1) x 8;   tU  batch x N x 2;   ok  batch ints.
+ * ltompc_get_jvp: host pointers.  A non-finite direction is a usage error that names the instance.
+ * ltompc_jvp_dev: device pointers, enqueues only, on the handle's stream.  The directions are NOT checked.  The first request
+ *   on a handle allocates the pass's buffers and synchronises once (as for ltompc_sensitivities_dev; the first one with dtheta
+ *   allocates the parameter part's the same way).
+ *
+ * The result refers to the last solve of each instance; before any solve and after set_initial_guess(_dev) a call is a usage
+ * error.  dtheta != NULL has the limits of ltompc_get_param_sensitivities: a handle with ell_penalty > 0 or ptv != 0, and a call
+ * after rollout_dev, are usage errors; dp alone is available there.  With per-instance rows the result is that at the rows the
+ * solve used.  The re-linearisation, the factorisation and the condensed right-hand sides are shared with the other passes
+ * (whichever runs first for a solve makes them); nothing is kept per direction.  The pass writes buffers of its own only: every
+ * later make_step, rollout or other pass gives the bits it would have given without it. */
+int ltompc_get_jvp(ltompc_handle h, const double* dp, const double* dtheta, double* tX, double* tU, int* ok);
+int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_dev, double* tX_dev, double* tU_dev, int* ok_dev);
+
+/* The previous input u_prev of the NEXT solve's Delta-u cost r_du (u_0 - u_prev)^2, which the handle otherwise makes itself (0
+ * after set_initial_guess, else the u0 the last make_step returned): with it the solve is a function of (x0, u_prev, theta) that
+ * a caller can evaluate.
+ *   u_prev  batch x 2, in the caller's instance order.
+ * ltompc_set_u_prev: host pointer.  Every row is checked finite; a bad row is a usage error that names the instance and leaves
+ *   the handle unchanged.  ltompc_set_u_prev_dev: a device pointer, enqueues only, on the handle's stream.  NOT checked.
+ * A set takes effect at the next make_step, make_step_dev or rollout_dev (there: the first solve of every instance) and holds
+ * for that solve only.  Made after set_initial_guess(_dev) it wins over the cold start's zero; a set_initial_guess(_dev) after it
+ * discards it.  It does not touch the warm start and does not invalidate the cached derivatives of the last solve, which keep
+ * referring to the u_prev that solve used. */
+int ltompc_set_u_prev(ltompc_handle h, const double* u_prev);
+int ltompc_set_u_prev_dev(ltompc_handle h, const double* u_prev_dev);
+
 /* Per-instance vehicle and cost parameters.  Instance b may have its own row theta_b: the LTOMPC_NTHETA = 16
  * values of ltompc_get_param_sensitivities' columns, in that order and in natural units.  Every other field of ltompc_params
  * stays the handle's.  Instance b's NLP, plant step and sensitivities are then bit for bit those of a handle created with

@@ -74,6 +74,10 @@ def lib() -> C.CDLL:
         L.ltompc_get_adjoint.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
         L.ltompc_adjoint_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_get_prediction_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_get_jvp.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
+        L.ltompc_jvp_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_set_u_prev.argtypes = [C.c_void_p, _dp]
+        L.ltompc_set_u_prev_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_set_instance_params.argtypes = [C.c_void_p, _dp]
         L.ltompc_set_instance_params_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_get_instance_params.argtypes = [C.c_void_p, _dp]

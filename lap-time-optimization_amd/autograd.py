@@ -1,0 +1,183 @@
+"""torch.autograd layer over a BatchedMPC handle: the solve and the plant step as differentiable functions of device tensors.
+
+    u0, X, U, ok = mpc_solve(mpc, x0, u_prev, theta)      # make_step_dev + prediction_dev; backward: adjoint_dev, forward mode: jvp_dev
+    x_next       = plant_step(mpc, x, u0, theta, n_sub)   # plant_sensitivities_dev; backward: its Jacobians through torch.einsum
+
+so that one tick `u0 = solve(x, u_prev, th); x = plant(x, u0, th)` is differentiable end to end and a T-tick loop backpropagates
+in plain torch.  Torch plumbing only: every number comes from the handle's kernels.
+
+All tensors are float64, contiguous and on the handle's device (`mpc.device`, the one device check; a stand-in handle with
+device "cpu" runs the layer on CPU tensors).  Streams, simple and safe: torch's current stream is synchronised before the handle
+is called and the handle after, so the layer neither overlaps with torch's work nor needs the handle on torch's stream.
+
+The handle is stateful: derivatives refer to ITS last solve.  mpc_solve records the handle's `solve_count`; backward / jvp raise
+a RuntimeError when another solve or initial guess has run on the handle since (solve, differentiate, then solve again; or use
+one handle per solve that is differentiated later).  Instances with ok = 0 give zero gradients, as the C interface does.
+"""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+NX, NU, NTHETA = 8, 2, 16
+
+
+def _check(mpc, name, t, shape):
+    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != torch.device(mpc.device):
+        raise ValueError(f"{name}: expected a contiguous float64 tensor of shape {shape} on {mpc.device}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
+def _sync_torch(mpc):
+    dev = torch.device(mpc.device)
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()
+
+
+def _new(mpc, *shape, dtype=torch.float64):
+    return torch.empty(shape, dtype=dtype, device=torch.device(mpc.device))
+
+
+def _dense(mpc, t, shape):
+    """a tangent or cotangent as the handle reads it (None: zeros)"""
+    if t is None:
+        return torch.zeros(shape, dtype=torch.float64, device=torch.device(mpc.device))
+    return t.to(torch.float64).expand(shape).contiguous()
+
+
+def _fresh(mpc, count, what):
+    if mpc.solve_count != count:
+        raise RuntimeError(f"mpc_solve {what}: another solve or initial guess has run on this handle since the solve being "
+                           f"differentiated (solve_count {mpc.solve_count}, recorded {count}); its derivatives are gone")
+
+
+class _Solve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mpc, x0, u_prev, theta):
+        B, N = mpc.B, mpc.N
+        _check(mpc, "mpc_solve: x0", x0, (B, NX))
+        if u_prev is not None:
+            _check(mpc, "mpc_solve: u_prev", u_prev, (B, NU))
+        if theta is not None:
+            _check(mpc, "mpc_solve: theta", theta, (B, NTHETA))
+        u0, X, U, ok = _new(mpc, B, NU), _new(mpc, B, N + 1, NX), _new(mpc, B, N, NU), _new(mpc, B, dtype=torch.int32)
+        _sync_torch(mpc)
+        if theta is not None:
+            mpc.set_theta_dev(theta.data_ptr())
+        if u_prev is not None:
+            mpc.set_u_prev_dev(u_prev.data_ptr())
+        mpc.make_step_dev(x0.data_ptr(), u0.data_ptr())
+        mpc.prediction_dev(X.data_ptr(), U.data_ptr())
+        mpc.sensitivities_dev(0, ok.data_ptr())  # (ok, and the factorisation that backward / jvp share)
+        mpc.synchronize()
+        ctx.mpc, ctx.count, ctx.has = mpc, mpc.solve_count, (u_prev is not None, theta is not None)
+        ctx.mark_non_differentiable(ok)
+        return u0, X, U, ok
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_u0, g_X, g_U, _g_ok):
+        mpc = ctx.mpc
+        _fresh(mpc, ctx.count, "backward")
+        B, N = mpc.B, mpc.N
+        gX = _dense(mpc, g_X, (B, N + 1, NX))
+        gU = _dense(mpc, g_U, (B, N, NU)).clone()
+        if g_u0 is not None:
+            gU[:, 0] += g_u0
+        want_theta = ctx.has[1] and ctx.needs_input_grad[3]
+        gp = _new(mpc, B, NX + NU)
+        gth = _new(mpc, B, NTHETA) if want_theta else None
+        _sync_torch(mpc)
+        mpc.adjoint_dev(gX.data_ptr(), gU.data_ptr(), gp.data_ptr(), gth.data_ptr() if want_theta else 0, 0)
+        mpc.synchronize()
+        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth
+
+    @staticmethod
+    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta):
+        mpc = ctx.mpc
+        _fresh(mpc, ctx.count, "jvp")
+        B, N = mpc.B, mpc.N
+        if not ctx.has[0]:
+            t_uprev = None
+        if not ctx.has[1]:
+            t_theta = None
+        dp = None
+        if t_x0 is not None or t_uprev is not None:
+            dp = torch.cat([_dense(mpc, t_x0, (B, NX)), _dense(mpc, t_uprev, (B, NU))], dim=1).contiguous()
+        dth = None if t_theta is None else _dense(mpc, t_theta, (B, NTHETA))
+        tX, tU = _new(mpc, B, N + 1, NX), _new(mpc, B, N, NU)
+        if dp is None and dth is None:
+            return _dense(mpc, None, (B, NU)), tX.zero_(), tU.zero_(), None
+        _sync_torch(mpc)
+        mpc.jvp_dev(dp.data_ptr() if dp is not None else 0, dth.data_ptr() if dth is not None else 0, tX.data_ptr(), tU.data_ptr(), 0)
+        mpc.synchronize()
+        return tU[:, 0].clone(), tX, tU, None
+
+
+class _Plant(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mpc, x, u, theta, n_sub):
+        B = mpc.B
+        _check(mpc, "plant_step: x", x, (B, NX))
+        _check(mpc, "plant_step: u", u, (B, NU))
+        if theta is not None:
+            _check(mpc, "plant_step: theta", theta, (B, NTHETA))
+        want_theta = theta is not None and ctx.needs_input_grad[3]
+        xn, dx, du = _new(mpc, B, NX), _new(mpc, B, NX, NX), _new(mpc, B, NX, NU)
+        dth = _new(mpc, B, NX, NTHETA) if want_theta else None
+        _sync_torch(mpc)
+        if theta is not None:
+            mpc.set_theta_dev(theta.data_ptr())
+        mpc.plant_sensitivities_dev(x.data_ptr(), u.data_ptr(), xn.data_ptr(), dx.data_ptr(), du.data_ptr(),
+                                    dth.data_ptr() if want_theta else 0, int(n_sub))
+        mpc.synchronize()
+        ctx.mpc, ctx.n_sub, ctx.dx, ctx.du, ctx.dth = mpc, int(n_sub), dx, du, dth
+        ctx.xu = (x.detach(), u.detach(), theta.detach()) if theta is not None else None  # (forward mode: dtheta on request, see jvp)
+        return xn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gx = torch.einsum("bi,bij->bj", g, ctx.dx)
+        gu = torch.einsum("bi,bij->bj", g, ctx.du)
+        gth = torch.einsum("bi,bij->bj", g, ctx.dth) if ctx.dth is not None and ctx.needs_input_grad[3] else None
+        return None, gx, gu, gth, None
+
+    @staticmethod
+    def jvp(ctx, _mpc, t_x, t_u, t_theta, _n_sub):
+        mpc = ctx.mpc
+        out = torch.zeros_like(ctx.dx[:, :, 0])
+        if t_x is not None:
+            out = out + torch.einsum("bij,bj->bi", ctx.dx, t_x)
+        if t_u is not None:
+            out = out + torch.einsum("bij,bj->bi", ctx.du, t_u)
+        if t_theta is not None and ctx.xu is not None:
+            dth = ctx.dth
+            if dth is None:  # (theta needed no gradient in reverse mode: its columns now, at the forward's rows, set again)
+                dth = _new(mpc, mpc.B, NX, NTHETA)
+                _sync_torch(mpc)
+                mpc.set_theta_dev(ctx.xu[2].data_ptr())
+                mpc.plant_sensitivities_dev(ctx.xu[0].data_ptr(), ctx.xu[1].data_ptr(), 0, 0, 0, dth.data_ptr(), ctx.n_sub)
+                mpc.synchronize()
+            out = out + torch.einsum("bij,bj->bi", dth, t_theta)
+        return out
+
+
+def mpc_solve(mpc, x0, u_prev=None, theta=None):
+    """One solve of the handle as a differentiable function: (u0 (B,2), X (B,N+1,8), U (B,N,2), ok (B,) int32) of x0 (B,8),
+    u_prev (B,2; None: the one the handle makes itself, no gradient) and theta (B,16 per-instance rows in THETA_NAMES order;
+    None: the rows or params in effect, no gradient).
+
+    Forward: set_theta_dev / set_u_prev_dev for the arguments given, make_step_dev, prediction_dev (and ok of the sensitivity
+    pass).  Backward: adjoint_dev with the cotangent of u0 added to gU[:, 0]; grad_theta is requested only when theta needs a
+    gradient.  Forward mode (torch.autograd.forward_ad): jvp_dev.  ok is not differentiable; where it is 0 all derivatives are 0.
+    Torch's current stream is synchronised before the calls and the handle after them."""
+    return _Solve.apply(mpc, x0, u_prev, theta)
+
+
+def plant_step(mpc, x, u, theta=None, n_sub=400):
+    """The plant step as a differentiable function: x_next (B,8; the bits of plant_step_dev) of x (B,8), u (B,2) and theta
+    (B,16 rows, set on the handle as set_theta_dev does; None: the rows or params in effect, no gradient).  Forward:
+    plant_sensitivities_dev (dxn_dtheta only when theta needs a gradient); backward contracts the stored Jacobians with
+    torch.einsum.  Same stream rule as mpc_solve."""
+    return _Plant.apply(mpc, x, u, theta, n_sub)

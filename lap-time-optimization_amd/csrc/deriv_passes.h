@@ -1,5 +1,5 @@
 // deriv_passes.h — host drivers and C entry points of the derivative passes on the final iterate of a solve:
-// sensitivities w.r.t. (x0, u_prev) and theta, the adjoint of a trajectory loss, the plant-step sensitivities and the closed loop.
+// sensitivities w.r.t. (x0, u_prev) and theta, the adjoint of a trajectory loss, their product with one direction, the plant-step sensitivities and the closed loop.
 // Part of ltompc.hip's translation unit, after ltompc_solver and its helpers; the passes' state is ltompc_solver::dv (DerivState).
 #pragma once
 
@@ -150,6 +150,29 @@ int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, co
   return 0;
 }
 
+// The directional pass of the last solve (jvp.h) for one direction (device pointers, caller's order; either may be null), into
+// tX_dev / tU_dev (either may be null): the factorisation and, with dtheta, the PV planes when not there, then one sweep.  Once
+// its kff planes exist it only enqueues.
+int jvp_compute(ltompc_solver* h, const double* dp_dev, const double* dth_dev, double* tX_dev, double* tU_dev, const char* who) {
+  DerivState& D = h->dv;
+  if (!dp_dev && !dth_dev) return fail(std::string(who) + ": dp and dtheta are both NULL (no direction)");
+  if (dth_dev ? psens_prepare(h, who) : sens_compute(h, false, who)) return -1;
+  const int N = h->N, Bp = h->Bp;
+  if (dth_dev && !D.d_jvp_jv) {
+    if (h->dalloc(&D.d_jvp_jv, (size_t)JV_NF * N * Bp, true)) return -1;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  }
+  dth_dev ? psens_condense(h) : sens_factorise(h);
+  if (h->pi_solve)
+    hipLaunchKernelGGL(k_jvp_sweep_pi, dim3(Bp / 8), dim3(64), 0, h->stream, D.Wspi, (const double*)D.d_psens_uprev, (const double*)D.d_psens_pv,
+                       (const int*)D.d_sens_ok, dp_dev, dth_dev, D.d_jvp_jv, tX_dev, tU_dev);
+  else
+    hipLaunchKernelGGL(k_jvp_sweep, dim3(Bp / 8), dim3(64), 0, h->stream, D.Ws, h->K.p.r_du[0], h->K.p.r_du[1], (const double*)D.d_psens_uprev,
+                       (const double*)D.d_psens_pv, (const int*)D.d_sens_ok, dp_dev, dth_dev, D.d_jvp_jv, tX_dev, tU_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 // k_plant_sens' planes and the row-major staging of the host forms and, with `loop`, the closed loop's state: each on the first
 // request, with one synchronisation.
 int psn_prepare(ltompc_solver* h, const bool loop) {
@@ -267,6 +290,39 @@ int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, doub
   if (adj_compute(h, gX ? D.d_adj_gX : nullptr, gU ? D.d_adj_gU : nullptr, grad_theta != nullptr, who)) return -1;
   if (copy_out(h, D2H, grad_p, D.d_adj_gp, ADJ_NP * B) || copy_out(h, D2H, grad_theta, D.d_adj_gth, PS_NT * B) ||
       copy_out(h, D2H, ok, D.d_sens_ok, B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_dev, double* tX_dev, double* tU_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (jvp_compute(h, dp_dev, dtheta_dev, tX_dev, tU_dev, "ltompc_jvp_dev")) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_jvp(ltompc_handle h, const double* dp, const double* dtheta, double* tX, double* tU, int* ok) {
+  const char* who = "ltompc_get_jvp";
+  if (!h) return fail("null handle");
+  if (!dp && !dtheta) return fail(std::string(who) + ": dp and dtheta are both NULL (no direction)");
+  const size_t B = h->B, N = h->N;
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; dp && e < JVP_NP; e++) fin = fin && std::isfinite(dp[b * JVP_NP + e]);
+    for (size_t e = 0; dtheta && e < PS_NT; e++) fin = fin && std::isfinite(dtheta[b * PS_NT + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite direction of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  DerivState& D = h->dv;
+  if (!D.d_jvp_dp && (h->dalloc(&D.d_jvp_dp, JVP_NP * B) || h->dalloc(&D.d_jvp_dth, PS_NT * B) || h->dalloc(&D.d_jvp_tX, (N + 1) * 8 * B) ||
+                      h->dalloc(&D.d_jvp_tU, N * 2 * B)))
+    return -1;
+  if (dp) HIPCHECK(hipMemcpyAsync(D.d_jvp_dp, dp, sizeof(double) * JVP_NP * B, hipMemcpyHostToDevice, h->stream));
+  if (dtheta) HIPCHECK(hipMemcpyAsync(D.d_jvp_dth, dtheta, sizeof(double) * PS_NT * B, hipMemcpyHostToDevice, h->stream));
+  if (jvp_compute(h, dp ? D.d_jvp_dp : nullptr, dtheta ? D.d_jvp_dth : nullptr, tX ? D.d_jvp_tX : nullptr, tU ? D.d_jvp_tU : nullptr, who))
+    return -1;
+  if (copy_out(h, D2H, tX, D.d_jvp_tX, (N + 1) * 8 * B) || copy_out(h, D2H, tU, D.d_jvp_tU, N * 2 * B) || copy_out(h, D2H, ok, D.d_sens_ok, B))
     return -1;
   HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;

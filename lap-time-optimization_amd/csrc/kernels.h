@@ -27,10 +27,12 @@
 //   adjoint.h     k_adj_sweep: the gradient of a loss of the predicted trajectory w.r.t. (x0, u_prev, theta) from its cotangents
 //                 (ltompc_get_adjoint): one backward / forward recursion of vectors on the same factorisation, contracted with
 //                 k_psens_cond's planes; k_prediction_dev: the prediction as device arrays in the caller's order
+//   jvp.h         k_jvp_sweep: the product of those Jacobians with one direction (dp, dtheta) (ltompc_get_jvp): the backward recursion
+//                 of the one dtheta-weighted vector and one forward pass on the same factorisation; k_set_uprev (ltompc_set_u_prev)
 //   plant_sensitivity.h k_plant_sens: the derivative of k_plant's discrete RK4 map w.r.t. (x, u, theta) (ltompc_plant_sensitivities);
 //                 k_loop_accum: the closed-loop recursion that chains it with the du0 outputs of the two forward passes over many
 //                 ticks (ltompc_loop_*)
-//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the four headers above
+//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the five headers above
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
@@ -46,4 +48,5 @@
 #include "sensitivity.h"
 #include "param_sensitivity.h"
 #include "adjoint.h"
+#include "jvp.h"
 #include "plant_sensitivity.h"

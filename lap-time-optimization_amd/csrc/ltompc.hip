@@ -66,6 +66,8 @@ struct DerivState {
   // adjoint pass (d_adj_gX / d_adj_gU stage the host form's cotangents), plant step (planes and their row-major staging), closed loop
   double *d_adj_aj = nullptr, *d_adj_gp = nullptr, *d_adj_gth = nullptr, *d_adj_gX = nullptr, *d_adj_gU = nullptr;
   double *d_psn_planes = nullptr, *d_psn_rm = nullptr, *d_loop_Sx = nullptr, *d_loop_Du = nullptr;
+  // directional pass (jvp.h): the kff planes, and the staging of the host form's directions and results
+  double *d_jvp_jv = nullptr, *d_jvp_dp = nullptr, *d_jvp_dth = nullptr, *d_jvp_tX = nullptr, *d_jvp_tU = nullptr;
   int *d_loop_ok = nullptr, *d_loop_ticks = nullptr;
 };
 
@@ -89,6 +91,7 @@ struct ltompc_solver {
   bool packing = true;  // LTOMPC_PACK=0: re-pack the list of unfinished instances only, leave their data where it is
   std::vector<int> history;  // (iteration, n_active, n_launch) triples of the last make_step's polls
   bool cold_next = true;
+  bool uprev_set = false;  // ltompc_set_u_prev since the last solve or initial guess: the next solve's cold start keeps W.uprev
   bool after_rollout = false;  // the last solve was a rollout: W.active holds no per-iteration counts
   int poll_every = 4;
   int profiling = 0;  // 0 off, 1 every launch bracketed, 2 + c: launches of kernel class c only
@@ -691,6 +694,7 @@ int ltompc_set_initial_guess_dev(ltompc_handle h, const double* x0_dev) {
   hipLaunchKernelGGL(k_init, dim3((h->N * h->Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, 1);
   HIPCHECK(hipGetLastError());
   h->cold_next = true;  // the next make_step starts from this guess
+  h->uprev_set = false;  // (a u_prev set before the guess is gone with the rest)
   return 0;
 }
 
@@ -700,6 +704,27 @@ int ltompc_set_initial_guess(ltompc_handle h, const double* x0) {
   HIPCHECK(hipMemcpyAsync(h->d_x0_rm, x0, sizeof(double) * 8 * h->B, hipMemcpyHostToDevice, h->stream));
   int rc = ltompc_set_initial_guess_dev(h, h->d_x0_rm);
   if (rc) return rc;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_set_u_prev_dev(ltompc_handle h, const double* u_prev_dev) {
+  if (!h || !u_prev_dev) return fail("ltompc_set_u_prev: null argument");
+  HIPCHECK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_set_uprev, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->W, u_prev_dev, (const int*)(h->packed ? h->d_orig : nullptr));
+  HIPCHECK(hipGetLastError());
+  h->uprev_set = true;
+  return 0;
+}
+
+int ltompc_set_u_prev(ltompc_handle h, const double* u_prev) {
+  if (!h || !u_prev) return fail("ltompc_set_u_prev: null argument");
+  for (int b = 0; b < h->B; b++)
+    if (!std::isfinite(u_prev[(size_t)b * 2]) || !std::isfinite(u_prev[(size_t)b * 2 + 1]))
+      return fail("ltompc_set_u_prev: non-finite u_prev of instance " + std::to_string(b));
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipMemcpyAsync(h->d_u0_rm, u_prev, sizeof(double) * 2 * h->B, hipMemcpyHostToDevice, h->stream));
+  if (ltompc_set_u_prev_dev(h, h->d_u0_rm)) return -1;
   HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -714,7 +739,8 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   if (commit_theta(h)) return -1;
   hipLaunchKernelGGL(k_load_x0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)(h->packed ? h->d_orig : nullptr),
                      h->K.o.resto_sticky, h->cold_next ? 0 : 1);
-  if (h->cold_next) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
+  if (h->cold_next && !h->uprev_set) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
+  h->uprev_set = false;
   if (!h->cold_next && h->K.o.warm_shift) {
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 0);
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 1);
@@ -893,7 +919,8 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   h->profiling = 0;  // (per-launch events are a make_step facility)
   Launcher L{h};
   hipLaunchKernelGGL(k_roll_begin, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, n_ticks);
-  if (h->cold_next) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
+  if (h->cold_next && !h->uprev_set) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
+  h->uprev_set = false;
   HIPCHECK(hipMemsetAsync(h->W.ls_count, 0, 2 * sizeof(int), h->stream));
   int cur = 0, n_launch = B;
   h->history.clear();

@@ -36,6 +36,8 @@ class BatchedMPC:
         self._theta_rows = None  # per-instance rows set (set_theta), (B, 16), None: the handle's params, _DEV_ROWS: set_theta_dev
         self._theta_solved = None  # ... those of the last solve (feedback(theta=...) expands around them)
         self._uprev_next = np.zeros((self.B, NU))
+        self.device = f"cuda:{int(device)}"  # torch's name of the handle's device (the one device check of autograd.py)
+        self.solve_count = 0  # solves and initial guesses so far: what a derivative of "the last solve" refers to (autograd.py)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -54,6 +56,23 @@ class BatchedMPC:
         check(lib().ltompc_set_initial_guess(self._h, dptr(x0)))
         self._solved, self._uprev_next = None, np.zeros((self.B, NU))
         self._fb = self._pfb = None
+        self.solve_count += 1
+
+    def set_u_prev(self, u_prev):
+        """The previous input (B,2) of the NEXT solve's Delta-u cost, in place of the one the handle makes itself (0 after
+        set_initial_guess, else the last u0); checked finite.  For that solve only; the warm start and the last solve's cached
+        derivatives stay.  solved_parameters() / feedback() then report it as that solve's u_prev."""
+        u = np.ascontiguousarray(np.asarray(u_prev, dtype=np.float64).reshape(-1, NU))
+        if u.shape[0] != self.B:
+            raise ValueError(f"set_u_prev: expected {self.B} inputs of dimension {NU}, got array of shape {u.shape}")
+        check(lib().ltompc_set_u_prev(self._h, dptr(u)))
+        self._uprev_next = u.copy()
+
+    def set_u_prev_dev(self, u_prev_ptr: int):
+        """set_u_prev from a device array of (B,2) float64 (ltompc_set_u_prev_dev): enqueued on the handle's stream, NOT checked.
+        The host then does not see the next solve's u_prev: solved_parameters() is None after it."""
+        check(lib().ltompc_set_u_prev_dev(self._h, C.c_void_p(u_prev_ptr)))
+        self._uprev_next = None
 
     def make_step(self, x0):
         x0 = self._x(x0)
@@ -64,6 +83,7 @@ class BatchedMPC:
         self._fb = self._pfb = None
         # (rows set from device memory: read back the ones this solve is about to use, for feedback(theta=...))
         theta_solve = self.instance_theta() if self._theta_rows is _DEV_ROWS else self._theta_rows
+        self.solve_count += 1
         check(lib().ltompc_make_step(self._h, dptr(x0), dptr(u0), iptr(self.status), iptr(self.iters)))
         self._theta_solved = theta_solve
         if self._uprev_next is not None:
@@ -79,10 +99,12 @@ class BatchedMPC:
         check(lib().ltompc_set_initial_guess_dev(self._h, C.c_void_p(x0_ptr)))
         self._solved, self._uprev_next = None, np.zeros((self.B, NU))
         self._fb = self._pfb = None
+        self.solve_count += 1
 
     def make_step_dev(self, x0_ptr: int, u0_ptr: int):
         self._solved = self._uprev_next = None
         self._fb = self._pfb = None
+        self.solve_count += 1
         check(lib().ltompc_make_step_dev(self._h, C.c_void_p(x0_ptr), C.c_void_p(u0_ptr)))
         self._theta_solved = None  # (feedback() needs a host make_step)
 
@@ -90,6 +112,7 @@ class BatchedMPC:
         """Closed-loop rollout with free-running instances (ltompc_rollout_dev): n_ticks of make_step + plant step per instance."""
         self._solved = self._uprev_next = None
         self._fb = self._pfb = None
+        self.solve_count += 1
         check(lib().ltompc_rollout_dev(self._h, C.c_void_p(x_ptr), int(n_ticks), int(n_sub), C.c_void_p(u_log_ptr or None),
                                        C.c_void_p(status_log_ptr or None), C.c_void_p(iters_log_ptr or None)))
         self._theta_solved = None  # (feedback() needs a host make_step)
@@ -181,6 +204,35 @@ class BatchedMPC:
         / (B,16) doubles / (B,) int32; grad_theta_ptr = 0 skips the parameter part of the pass."""
         check(lib().ltompc_adjoint_dev(self._h, C.c_void_p(gX_ptr or None), C.c_void_p(gU_ptr or None), C.c_void_p(grad_p_ptr or None),
                                        C.c_void_p(grad_theta_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    # ---- directional sensitivities: the Jacobians times one direction (ltompc_get_jvp, DESIGN.md §13) ----------------------
+    def jvp(self, dp=None, dtheta=None):
+        """Directional derivative of the last solve's predicted trajectory along dp (B,10: x0[0..7], u_prev[0..1]) and dtheta
+        (B,16, THETA_NAMES order, natural units) (None: zeros; not both): the contraction of sensitivities(trajectory=True) and
+        param_sensitivities(trajectory=True) with the direction, in one sweep and without the Jacobians.
+
+        Returns tX (B,N+1,8; block 0 is dp[:, :8]), tU (B,N,2), ok (B,) bool (the same as sensitivities()' ok).  Where ok is
+        False every output of the instance is 0."""
+        B, N = self.B, self.N
+        if dp is not None:
+            dp = np.ascontiguousarray(dp, dtype=np.float64)
+            if dp.shape != (B, 10):
+                raise ValueError(f"jvp: dp must have shape {(B, 10)}, got {dp.shape}")
+        if dtheta is not None:
+            dtheta = np.ascontiguousarray(dtheta, dtype=np.float64)
+            if dtheta.shape != (B, NTHETA):
+                raise ValueError(f"jvp: dtheta must have shape {(B, NTHETA)}, got {dtheta.shape}")
+        tX, tU, ok = np.empty((B, N + 1, NX)), np.empty((B, N, NU)), np.empty(B, dtype=np.int32)
+        check(lib().ltompc_get_jvp(self._h, dptr(dp) if dp is not None else None, dptr(dtheta) if dtheta is not None else None,
+                                   dptr(tX), dptr(tU), iptr(ok)))
+        return dict(tX=tX, tU=tU, ok=ok != 0)
+
+    def jvp_dev(self, dp_ptr: int, dtheta_ptr: int, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue the directional pass of the last solve on the handle's stream: directions from device arrays (B,10) / (B,16)
+        of doubles (0: zeros; not both, NOT checked for finiteness), results into device arrays (B,N+1,8) / (B,N,2) doubles /
+        (B,) int32; dtheta_ptr = 0 skips the parameter part of the pass."""
+        check(lib().ltompc_jvp_dev(self._h, C.c_void_p(dp_ptr or None), C.c_void_p(dtheta_ptr or None), C.c_void_p(tX_ptr or None),
+                                   C.c_void_p(tU_ptr or None), C.c_void_p(ok_ptr or None)))
 
     def prediction_dev(self, X_ptr: int = 0, U_ptr: int = 0):
         """Enqueue a copy of the last solve's prediction into device arrays (B,N+1,8) / (B,N,2) of doubles in the caller's
@@ -645,6 +697,36 @@ class SplitMPC:
             p.adjoint_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0,
                           grad_p_ptr + 8 * 10 * lo if grad_p_ptr else 0, grad_theta_ptr + 8 * NTHETA * lo if grad_theta_ptr else 0,
                           ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def jvp(self, dp=None, dtheta=None):
+        """BatchedMPC.jvp of every part with its rows of the directions, stitched in the caller's order."""
+        dp = None if dp is None else np.asarray(dp, dtype=np.float64)
+        dtheta = None if dtheta is None else np.asarray(dtheta, dtype=np.float64)
+        r = [p.jvp(None if dp is None else dp[lo:hi], None if dtheta is None else dtheta[lo:hi]) for p, (lo, hi) in zip(self.parts, self.bounds)]
+        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    def jvp_dev(self, dp_ptr: int, dtheta_ptr: int, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.jvp_dev of every part on its rows of (B,10) / (B,16) directions into its rows of (B,N+1,8) / (B,N,2)
+        doubles / (B,) int32, each on its part's stream."""
+        N = self.N
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.jvp_dev(dp_ptr + 8 * 10 * lo if dp_ptr else 0, dtheta_ptr + 8 * NTHETA * lo if dtheta_ptr else 0,
+                      tX_ptr + 8 * (N + 1) * NX * lo if tX_ptr else 0, tU_ptr + 8 * N * NU * lo if tU_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def set_u_prev(self, u_prev):
+        """BatchedMPC.set_u_prev with the rows split across the parts."""
+        u = np.asarray(u_prev, dtype=np.float64).reshape(-1, NU)
+        if u.shape[0] != self.B:
+            raise ValueError(f"set_u_prev: expected {self.B} inputs of dimension {NU}, got array of shape {u.shape}")
+        if not np.isfinite(u).all():  # (the whole batch checked first: a bad row changes no part)
+            raise ValueError(f"set_u_prev: non-finite u_prev of instance {int(np.argwhere(~np.isfinite(u))[0][0])}")
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.set_u_prev(u[lo:hi])
+
+    def set_u_prev_dev(self, u_prev_ptr: int):
+        """BatchedMPC.set_u_prev_dev of every part on its rows of (B,2) doubles, each on its part's stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.set_u_prev_dev(u_prev_ptr + 8 * NU * lo)
 
     def plant_sensitivities(self, x, u, n_sub: int = 400, theta: bool = True):
         """BatchedMPC.plant_sensitivities of every part on its rows, stitched in the caller's order."""
