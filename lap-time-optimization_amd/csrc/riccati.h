@@ -1253,8 +1253,13 @@ __host__ __device__ constexpr size_t ric1q_lds_bytes(int N) { return sizeof(doub
 // Workgroup barrier for data exchanged through LDS only: waits for the wavefront's own LDS operations (lgkmcnt), NOT for its
 // outstanding global stores - __syncthreads() also drains vmcnt, and every barrier of a stage would then wait for the Riccati
 // words the stage has just stored to HBM (measured: a stage of k_riccati1q 3500 cycles with __syncthreads()).
+#if defined(LTOMPC_HARNESS_WORKGROUP)  // (a workgroup barrier of the harness's lock-step workgroup, hip_shim.h)
+#define WG_SYNC_LDS() lt_barrier("WG_SYNC_LDS", __FILE__, __LINE__)
+#elif defined(LTOMPC_HOST_HARNESS)  // (a shim without the lock-step workgroup compiles the kernel and cannot run it)
+#define WG_SYNC_LDS() ((void)0)
+#else
 #define WG_SYNC_LDS() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#if !defined(LTOMPC_HOST_HARNESS)
+#endif
 template <bool PI = false>
 __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1qLds& X, const StageLds& S, const int t, const int b,
                                             const int active_slot, const int max_sweeps) {
@@ -1605,7 +1610,6 @@ __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1
   if (rprof) W.DBG[4] += 1.0;
 #undef RTOCK
 }
-#endif
 
 __global__ void __launch_bounds__(64) k_riccati8(Consts K, Work W, Launch la, int it_index, int max_sweeps) {
   __shared__ RicLds L;
@@ -1617,16 +1621,18 @@ __global__ void __launch_bounds__(64) k_riccati8(Consts K, Work W, Launch la, in
 
 // Four wavefronts per instance (see d_riccati1q): dynamic LDS ric1q_lds_bytes(N).
 __global__ void __launch_bounds__(256) k_riccati1q(Consts K, Work W, Launch la, int it_index, int max_sweeps) {
-#if defined(LTOMPC_HOST_HARNESS)
-  (void)K, (void)W, (void)la, (void)it_index, (void)max_sweeps;  // (never run by the harness)
+#if defined(LTOMPC_HARNESS_WORKGROUP)
+  double* const lds1q = static_cast<double*>(lt_dyn_lds);  // ric1q_lds_bytes(N) at its exact size, allocated per block by the harness
+#elif defined(LTOMPC_HOST_HARNESS)
+  static double lds1q[1];  // (a shim without the lock-step workgroup only compiles this)
 #else
   extern __shared__ double lds1q[];
+#endif
   if ((int)blockIdx.x >= la.nact[0]) return;
   const int N = W.N;
   StageLds S{lds1q, lds1q + (size_t)N * QP_NF, lds1q + (size_t)N * (QP_NF + 2)};
   Ric1qLds& X = *reinterpret_cast<Ric1qLds*>(lds1q + (size_t)N * (QP_NF + 24));
   d_riccati1q(K, W, X, S, threadIdx.x, la.act[blockIdx.x], it_index, max_sweeps);
-#endif
 }
 
 // One wavefront per instance (narrow launches: once few instances are left, a launch is as long as one wavefront's
@@ -1657,16 +1663,18 @@ __global__ void __launch_bounds__(64) k_riccati8_pi(Consts K, WorkPI W, Launch l
   d_riccati8<false, true>(K, W, L, g, i, la.act[valid ? jj : 0], valid, it_index, max_sweeps);
 }
 __global__ void __launch_bounds__(256) k_riccati1q_pi(Consts K, WorkPI W, Launch la, int it_index, int max_sweeps) {
-#if defined(LTOMPC_HOST_HARNESS)
-  (void)K, (void)W, (void)la, (void)it_index, (void)max_sweeps;  // (never run by the harness)
+#if defined(LTOMPC_HARNESS_WORKGROUP)
+  double* const lds1q = static_cast<double*>(lt_dyn_lds);  // ric1q_lds_bytes(N) at its exact size, allocated per block by the harness
+#elif defined(LTOMPC_HOST_HARNESS)
+  static double lds1q[1];  // (a shim without the lock-step workgroup only compiles this)
 #else
   extern __shared__ double lds1q[];
+#endif
   if ((int)blockIdx.x >= la.nact[0]) return;
   const int N = W.N;
   StageLds S{lds1q, lds1q + (size_t)N * QP_NF, lds1q + (size_t)N * (QP_NF + 2)};
   Ric1qLds& X = *reinterpret_cast<Ric1qLds*>(lds1q + (size_t)N * (QP_NF + 24));
   d_riccati1q<true>(K, W, X, S, threadIdx.x, la.act[blockIdx.x], it_index, max_sweeps);
-#endif
 }
 __global__ void __launch_bounds__(64) k_riccati1_pi(Consts K, WorkPI W, Launch la, int it_index, int max_sweeps) {
 #if defined(LTOMPC_HARNESS_WAVEFRONT)

@@ -3,11 +3,19 @@
 // 4: zero-filled device buffers would hide reads of words no kernel has written; the pool's GPUs run no sanitizer).
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -DLTOMPC_HOST_HARNESS -I<csrc> -I<harness> ...
 // Reads a problem from a text file (tables, x0 batch, horizon, options; sections `rows`, `cot`, `u`), runs the interior-point
-// iterations with the launch sequence of ltompc_make_step_dev (no re-packing, no k_step1), prints status / iterations / u0 per
-// instance.  tests/test_host_harness*.py compare that with the oracle and the dense references.  key=value arguments:
-//   riccati=serial|8|1   k_riccati (default; LTOMPC_RICCATI=serial), k_riccati8 over Bp / 8 waves, k_riccati1 one wave per instance
+// iterations with the launch sequence of ltompc_make_step_dev, prints status / iterations / u0 per instance.  tests/test_host_harness*.py compare that with the oracle and the dense references.  key=value arguments:
+//   riccati=serial|8|1|1q  k_riccati (default; LTOMPC_RICCATI=serial), k_riccati8 over Bp / 8 waves, k_riccati1 one wave per instance,
+//                        k_riccati1q one workgroup of four wavefronts per instance (dynamic LDS of exactly ric1q_lds_bytes(N))
+//   step=1               k_step1 (320 lanes per listed instance) instead of k_linesearch / k_pick / k_linesearch / k_pick / k_update
 //   eval=slot|8          k_eval / k_expand (default) or k_eval8 / k_expand8
-//   compact=1            the instance list is the stable compaction of the unfinished instances after every iteration
+//   compact=1|kernel     the instance list is the stable compaction of the unfinished instances after every iteration: made by a
+//                        host loop (1) or by k_compact itself with ping-pong lists (kernel)
+//   pack=1 pack_min=<n>  re-packing by the library's rule: k_pack_perm + k_pack while the launch is wider than n (the library: 512),
+//                        k_compact below; the packed order is kept between ticks; k_pack_inverse + k_pack after the last tick
+//   rollout=<ticks>      ltompc_rollout_dev's loop on one stream (k_roll_begin / _mark / _init / _finish / _plant, k_compact on SI_FINAL)
+//   wave_order=asc|desc  the order in which the wavefronts of a workgroup run between two barriers (hip_shim.h)
+//   final=1              one more block after the last tick: the state the run leaves behind
+//   - selftest=<case>, - scan   (no problem file) the executor's self-test; k_compact / k_pack_perm against a plain stable partition
 //   section rows         per-instance rows through k_theta_rows, WorkPI and the _pi kernels; param.<field>=<value> for uniform runs
 //   derivs=1 dump=<file> after each tick's solve the passes of sens_compute / psens_compute / adj_compute, everything as raw doubles
 //   loop=<mode>          with derivs=1: k_loop_begin, per tick k_plant_sens and k_loop_accum
@@ -15,13 +23,17 @@
 //   model_eps=<eps>, slip=1, ellipse=1   k_test_model / k_slip_forces / k_test_ellipse at given points (tests/test_synthetic_tracks.py)
 //   velocity             (the only argument, with a file of its own format: velocity_mode below) k_velocity_profile
 // What runs: the thread-per-slot kernels lane after lane; on the lock-step wavefront of hip_shim.h k_riccati8, k_riccati1,
-// k_eval8, k_expand8, k_pick, k_sens_eval8, k_sens_riccati8, k_sens_forward, k_psens_sweep, k_adj_sweep; the _pi form of each.
-// What does not: k_riccati1q, k_step1, k_compact / k_pack*, the rollout kernels (workgroups of several wavefronts).  NOT a product path and not an oracle: nothing in the package or in bench.py uses it.
+// k_eval8, k_expand8, k_pick, k_sens_eval8, k_sens_riccati8, k_sens_forward, k_psens_sweep, k_adj_sweep; on its lock-step
+// workgroup of several wavefronts k_riccati1q, k_step1, k_compact, k_pack_perm; the _pi form of each; k_pack, k_pack_inverse and
+// the rollout kernels lane after lane.  Not modelled: several lanes adding to one LDS word in the same instruction, the ordering
+// of global memory between workgroups, the rollout's two streams (the plant kernel of a pass runs after the pass).
+// NOT a product path and not an oracle: nothing in the package or in bench.py uses it.
 #include "layout.h"
 #include "linearise.h"
 #include "riccati.h"
 #include "linesearch.h"
 #include "aux_kernels.h"
+#include "rollout.h"
 #include "velocity.h"
 #include "eval8.h"
 #include "sensitivity.h"
@@ -113,35 +125,37 @@ static void grid_bs(size_t threads, unsigned bs, F&& body) {
   blockDim.x = 64;
 }
 static double* zeros(size_t n) { return (double*)calloc(n ? n : 1, sizeof(double)); }  // (what the library allocates without `work`)
-// run a one-wavefront kernel body on the lock-step wavefront (hip_shim.h), the blocks one after the other
+// run a kernel body on the lock-step workgroup of hip_shim.h, the blocks one after the other: `threads` lanes (a multiple of 64)
+// per block, fiber stacks of `stack` bytes, and `extern __shared__` of lds_bytes (0: none) as a fresh NaN-filled buffer of
+// exactly that size for every block
 template <typename F>
-static void wave64(const char* name, int blocks, F&& body) {
-  blockDim.x = 64, gridDim.x = blocks;
+static void wg(const char* name, int blocks, int threads, size_t lds_bytes, size_t stack, F&& body) {
+  blockDim.x = threads, gridDim.x = blocks;
   for (int blk = 0; blk < blocks; blk++) {
     blockIdx.x = blk;
-    LtWave::self().run(name, [](void* p) { (*static_cast<std::remove_reference_t<F>*>(p))(); }, &body);
+    void* lds = nullptr;
+    if (lds_bytes) lds = malloc(lds_bytes), memset(lds, 0xFF, lds_bytes);
+    lt_dyn_lds = lds;
+    LtWave::self().run(name, threads / 64, stack, [](void* p) { (*static_cast<std::remove_reference_t<F>*>(p))(); }, &body);
+    lt_dyn_lds = nullptr;
+    free(lds);
   }
+  blockDim.x = 64;
 }
+// ... one wavefront per block
+template <typename F>
+static void wave64(const char* name, int blocks, F&& body) { wg(name, blocks, 64, 0, LtWave::STACK, body); }
 template <typename F>
 static void wave64y(const char* name, int bx, int by, F&& body) {  // grid (bx, by)
   gridDim.y = by;
   for (int y = 0; y < by; y++) blockIdx.y = y, wave64(name, bx, body);
   gridDim.y = 1, blockIdx.y = 0;
 }
-// ... with `extern __shared__` of lds_bytes: a fresh NaN-filled buffer of exactly that size for every block
 template <typename F>
-static void wave64_lds(const char* name, int blocks, size_t lds_bytes, F&& body) {
-  blockDim.x = 64, gridDim.x = blocks;
-  for (int blk = 0; blk < blocks; blk++) {
-    blockIdx.x = blk;
-    void* lds = malloc(lds_bytes);
-    memset(lds, 0xFF, lds_bytes);
-    lt_dyn_lds = lds;
-    LtWave::self().run(name, [](void* p) { (*static_cast<std::remove_reference_t<F>*>(p))(); }, &body);
-    lt_dyn_lds = nullptr;
-    free(lds);
-  }
-}
+static void wave64_lds(const char* name, int blocks, size_t lds_bytes, F&& body) { wg(name, blocks, 64, lds_bytes, LtWave::STACK, body); }
+// ... the 1024-lane scan kernels (k_compact, k_pack_perm): one block, small stacks
+template <typename F>
+static void scan1024(const char* name, F&& body) { wg(name, 1, 1024, 0, LtWave::STACK_SMALL, body); }
 // the 16 fields of theta (ltompc_get_param_sensitivities' columns): param.<name>=<value>
 static const char* const THETA_NAMES[LTOMPC_NTHETA] = {"mass", "inertia_z", "B_f", "C_f", "D_f", "B_r", "C_r", "D_r", "C_m", "Cr_0", "Cr_2",
                                                        "q_n", "q_mu", "q_B", "r_du0", "r_du1"};
@@ -198,9 +212,116 @@ static int velocity_mode(const char* path) {
   return 0;
 }
 
+// ---- self-test of the lock-step workgroup (hip_shim.h): `harness - selftest=<case> [wave_order=asc|desc]`.  A kernel of two
+// wavefronts, here and not in csrc/: thread 64 (wavefront 1) writes an LDS word, thread 0 (wavefront 0) reads it.
+//   barrier           a __syncthreads() between the write and the read: both wavefront orders print `value 7`
+//   nobarrier         the barrier compiled out: the orders print different values - how a missing barrier shows
+//   diverged_barrier  a barrier inside `if (threadIdx.x < 64)` while the other lanes wait at a later one: MISMATCHED, exit status 3
+//   diverged_shfl     a __shfl that half a wavefront reaches while the other half has returned: MISMATCHED, exit status 3
+enum { SELF_BARRIER = 0, SELF_NOBARRIER, SELF_DIVERGED_BARRIER, SELF_DIVERGED_SHFL };
+template <int CASE>
+__global__ void k_selftest(int* out) {
+  __shared__ int word;
+  const int t = threadIdx.x;
+  if (t == 0) word = 0;
+  __syncthreads();
+  if (CASE == SELF_DIVERGED_SHFL) {
+    if ((t & 63) < 32) out[0] = __shfl(t, 0);
+    return;
+  }
+  if (t == 64) word = 7;
+  if (CASE == SELF_DIVERGED_BARRIER) {
+    if (t < 64) __syncthreads();
+  }
+  if (CASE != SELF_NOBARRIER) __syncthreads();
+  if (t == 0) out[0] = word;
+}
+static int selftest_mode(const char* which) {
+  int out[1] = {-1};
+  const std::string c(which);
+  if (c == "barrier") wg("k_selftest<barrier>", 1, 128, 0, LtWave::STACK_SMALL, [&] { k_selftest<SELF_BARRIER>(out); });
+  else if (c == "nobarrier") wg("k_selftest<nobarrier>", 1, 128, 0, LtWave::STACK_SMALL, [&] { k_selftest<SELF_NOBARRIER>(out); });
+  else if (c == "diverged_barrier") wg("k_selftest<diverged_barrier>", 1, 128, 0, LtWave::STACK_SMALL, [&] { k_selftest<SELF_DIVERGED_BARRIER>(out); });
+  else if (c == "diverged_shfl") wg("k_selftest<diverged_shfl>", 1, 128, 0, LtWave::STACK_SMALL, [&] { k_selftest<SELF_DIVERGED_SHFL>(out); });
+  else return fprintf(stderr, "harness: selftest=barrier|nobarrier|diverged_barrier|diverged_shfl\n"), 2;
+  printf("value %d\n", out[0]);
+  return 0;
+}
+
+// ---- scan mode: `harness - scan [wave_order=asc|desc]`.  k_compact and k_pack_perm outside a solve, on flag arrays of the sizes
+// 0, 1, 9, 1023, 1024, 1025 and 2500 (above 1024 a thread's chunk is 2 or 3 elements and the last threads' chunks are empty) with
+// the patterns all finished / none finished / alternating / only the last element unfinished / seeded random, against a plain
+// stable partition.  Every array at its exact size (the outputs too: dst has as many entries as there are unfinished elements),
+// the outputs filled with -1.  One line per case with the outputs' sums; a difference ends the run with exit status 1.
+static int* exact_ints(const std::vector<int>& v) {
+  int* p = (int*)malloc(v.size() * sizeof(int));
+  if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(int));
+  return p;
+}
+static int scan_mode() {
+  const int sizes[] = {0, 1, 9, 1023, 1024, 1025, 2500};
+  const char* const patterns[] = {"all_finished", "none_finished", "alternating", "last_unfinished", "random"};
+  uint64_t rng = 0x9E3779B97F4A7C15ull;
+  const auto next = [&] { return rng = rng * 6364136223846793005ull + 1442695040888963407ull, (unsigned)(rng >> 33); };
+  int bad = 0;
+  for (const int n : sizes)
+    for (int pat = 0; pat < 5; pat++) {
+      std::vector<int> flag(n);  // finished?
+      for (int j = 0; j < n; j++) flag[j] = pat == 0 ? 1 : pat == 1 ? 0 : pat == 2 ? (j & 1) : pat == 3 ? (j != n - 1) : (int)(next() & 1);
+      // k_compact: a list of n distinct instances (a seeded permutation of 0 .. n + 6, so that list position != instance index)
+      const int M = n + 7;
+      std::vector<int> ids(M), src(n), done(M, 1);
+      for (int j = 0; j < M; j++) ids[j] = j;
+      for (int j = M - 1; j > 0; j--) std::swap(ids[j], ids[next() % (j + 1)]);
+      for (int j = 0; j < n; j++) src[j] = ids[j], done[ids[j]] = flag[j];
+      std::vector<int> want;
+      for (int j = 0; j < n; j++)
+        if (!flag[j]) want.push_back(src[j]);
+      {
+        int *d_src = exact_ints(src), *d_done = exact_ints(done), *d_n = exact_ints({n});
+        int *dst = exact_ints(std::vector<int>(want.size(), -1)), *ndst = exact_ints({-1});
+        scan1024("k_compact", [&] { k_compact(d_src, d_n, d_done, dst, ndst); });
+        bool ok = ndst[0] == (int)want.size();
+        long long sum = 0;
+        for (size_t j = 0; j < want.size(); j++) ok = ok && dst[j] == want[j], sum += (long long)(j + 1) * dst[j];
+        printf("k_compact n=%d %s ndst=%d sum=%lld %s\n", n, patterns[pat], ndst[0], sum, ok ? "ok" : "MISMATCH");
+        bad += !ok;
+        free(d_src), free(d_done), free(d_n), free(dst), free(ndst);
+      }
+      // k_pack_perm: the first n slots, unfinished ones first (stable), then the finished ones (stable); act = identity over the unfinished
+      std::vector<int> perm_want;
+      for (int j = 0; j < n; j++)
+        if (!flag[j]) perm_want.push_back(j);
+      const int n_act = (int)perm_want.size();
+      for (int j = 0; j < n; j++)
+        if (flag[j]) perm_want.push_back(j);
+      {
+        int *d_done = exact_ints(flag), *d_n = exact_ints({n});
+        int *perm = exact_ints(std::vector<int>(n, -1)), *act = exact_ints(std::vector<int>(n_act, -1)), *nact = exact_ints({-1});
+        scan1024("k_pack_perm", [&] { k_pack_perm(d_n, d_done, perm, act, nact); });
+        bool ok = nact[0] == n_act;
+        long long sum = 0;
+        for (int j = 0; j < n; j++) ok = ok && perm[j] == perm_want[j], sum += (long long)(j + 1) * perm[j];
+        for (int j = 0; j < n_act; j++) ok = ok && act[j] == j;
+        printf("k_pack_perm n=%d %s nact=%d sum=%lld %s\n", n, patterns[pat], nact[0], sum, ok ? "ok" : "MISMATCH");
+        bad += !ok;
+        free(d_done), free(d_n), free(perm), free(act), free(nact);
+      }
+    }
+  return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return fprintf(stderr, "usage: harness problem.txt\n"), 2;
   if (argc == 3 && !strcmp(argv[2], "velocity")) return velocity_mode(argv[1]);
+  for (int a = 2; a < argc; a++)  // wave_order=asc|desc: the order in which the wavefronts of a workgroup run between two barriers (hip_shim.h)
+    if (!strncmp(argv[a], "wave_order=", 11)) {
+      const std::string v(argv[a] + 11);
+      if (v != "asc" && v != "desc") return fprintf(stderr, "harness: wave_order=asc|desc\n"), 2;
+      LtWave::self().desc_waves = v == "desc";
+    }
+  if (argc >= 3 && !strncmp(argv[2], "selftest=", 9)) return selftest_mode(argv[2] + 9);
+  if (argc >= 3 && !strcmp(argv[2], "scan")) return scan_mode();
   FILE* f = fopen(argv[1], "r");
   if (!f) return 2;
   int nt, N, B, any_bounds, ticks;
@@ -240,12 +361,20 @@ int main(int argc, char** argv) {
   const char* dump_path = nullptr;
   bool slip_mode = false, ellipse_mode = false;  // slip=1 / ellipse=1: k_slip_forces / k_test_ellipse at the states of the batch (below)
   bool compact = false;     // compact=1: the instance list is the stable compaction of the unfinished instances (what k_compact computes)
+  bool compact_kernel = false;  // compact=kernel: ... made by k_compact itself (1024 lanes), ping-pong lists as in ltompc_make_step_dev
+  bool ric1q = false;       // riccati=1q: k_riccati1q, one workgroup of four wavefronts per listed instance
+  bool step1 = false;       // step=1: k_step1 (320 lanes per listed instance) instead of k_linesearch / k_pick / k_linesearch / k_pick / k_update
+  bool pack = false;        // pack=1: re-packing by the library's rule (k_pack_perm, k_pack; the order is kept between ticks), un-packing at the end
+  int pack_min = 512;       // pack_min=<n>: launches wider than this move the instances, narrower ones only compact the list (the library: 512)
+  const int pack_num = 6;   // (ltompc.hip: re-pack when at most pack_num / 8 of the launch width is unfinished)
+  int rollout = 0;          // rollout=<ticks>: the loop of ltompc_rollout_dev, rendered sequentially, instead of synchronous ticks
+  bool final_block = false; // final=1: after the last tick one more block with the state the run leaves behind
   for (int a = 2; a < argc; a++) {
     if (!strncmp(argv[a], "model_eps=", 10)) { model_eps = atof(argv[a] + 10); continue; }
     if (!strncmp(argv[a], "riccati=", 8)) {
       const std::string v(argv[a] + 8);
-      ric = v == "serial" ? 0 : v == "8" ? 8 : v == "1" ? 1 : -1;
-      if (ric < 0) return fprintf(stderr, "harness: riccati=serial|8|1\n"), 2;
+      ric = v == "serial" ? 0 : v == "8" ? 8 : (v == "1" || v == "1q") ? 1 : -1, ric1q = v == "1q";
+      if (ric < 0) return fprintf(stderr, "harness: riccati=serial|8|1|1q\n"), 2;
       continue;
     }
     if (!strncmp(argv[a], "eval=", 5)) {
@@ -254,7 +383,13 @@ int main(int argc, char** argv) {
       eval8 = v == "8";
       continue;
     }
-    if (!strncmp(argv[a], "compact=", 8)) { compact = atoi(argv[a] + 8) != 0; continue; }
+    if (!strncmp(argv[a], "compact=", 8)) { compact_kernel = !strcmp(argv[a] + 8, "kernel"), compact = atoi(argv[a] + 8) != 0; continue; }
+    if (!strncmp(argv[a], "step=", 5)) { step1 = atoi(argv[a] + 5) != 0; continue; }
+    if (!strncmp(argv[a], "pack=", 5)) { pack = atoi(argv[a] + 5) != 0; continue; }
+    if (!strncmp(argv[a], "pack_min=", 9)) { pack_min = atoi(argv[a] + 9); continue; }
+    if (!strncmp(argv[a], "rollout=", 8)) { rollout = atoi(argv[a] + 8); continue; }
+    if (!strncmp(argv[a], "final=", 6)) { final_block = atoi(argv[a] + 6) != 0; continue; }
+    if (!strncmp(argv[a], "wave_order=", 11)) continue;  // (read before the modes)
     if (!strncmp(argv[a], "derivs=", 7)) { derivs = atoi(argv[a] + 7) != 0; continue; }
     if (!strncmp(argv[a], "loop=", 5)) { loop_mode = atoi(argv[a] + 5); continue; }
     if (!strncmp(argv[a], "plant_sens=", 11)) { plant_sens = atoi(argv[a] + 11); continue; }
@@ -329,11 +464,12 @@ int main(int argc, char** argv) {
   W.si = ipoisoned((size_t)SI_NF * bp, 0), W.active = ipoisoned(K.o.max_iter + 2, 0), W.ls_list = ipoisoned(bp, -1), W.ls_count = ipoisoned(4, 0);
   W.DBG = nullptr;
   W.BK = poisoned(18 * n * bp);
-  {
-    int* orig = ipoisoned(bp, -1);
-    for (int b = 0; b < B; b++) orig[b] = b;
-    W.orig = orig;
-  }
+  int* const d_orig = ipoisoned(bp, -1);  // slot -> caller's index (pack=1 permutes it with the instances)
+  for (int b = 0; b < B; b++) d_orig[b] = b;
+  W.orig = d_orig;
+  int* const d_perm = ipoisoned(bp, -1);
+  bool packed = false;
+  int n_packs = 0;  // re-packings that moved instances (final=1 prints it: a test of pack=1 that never packed would prove nothing)
   const bool ref = !any_bounds, el = K.bd.nel > 0;
   // Per-instance rows (ltompc_set_instance_params): a [16][Bp] plane with the handle's values in every column (theta_prepare),
   // the rows through k_theta_rows, WorkPI = W + TH (sync_pi_work) and the _pi kernels on every path below.
@@ -360,12 +496,14 @@ int main(int argc, char** argv) {
   std::vector<int> act(Bp), nact(1, B);
   for (int b = 0; b < Bp; b++) act[b] = b;
   // exact sizes for the list as well (the library's lists have Bp entries)
-  int* d_act = ipoisoned(bp, -1);
-  int* d_nact = ipoisoned(1, B);
-  memcpy(d_act, act.data(), sizeof(int) * bp);
-  Launch la{d_act, d_nact, Bp, 0};
+  int* const d_actl[2] = {ipoisoned(bp, -1), ipoisoned(bp, -1)};  // (ping-pong, as the library's d_act / d_nact)
+  int* const d_nactl[2] = {ipoisoned(1, B), ipoisoned(1, 0)};
+  memcpy(d_actl[0], act.data(), sizeof(int) * bp);
+  int cur = 0;
+  Launch la{d_actl[0], d_nactl[0], Bp, 0};
   int n_launch = B;
-  // the kernels of one iteration (launch_iteration_t of ltompc.hip, without the k_step1 / k_riccati1q branches)
+  const auto set_list = [&](const int c, const int n) { cur = c, la.act = d_actl[c], la.nact = d_nactl[c], n_launch = n; };
+  // the kernels of one iteration (launch_iteration_t of ltompc.hip)
   const auto run_eval = [&] {
     if (eval8) {
       if (PI) wave64("k_eval8_pi", N * Bp / 8, [&] { k_eval8_pi(&K, &Wpi, la); });
@@ -395,9 +533,37 @@ int main(int argc, char** argv) {
       else wave64("k_riccati8", Bp / 8, [&] { k_riccati8(K, W, la, it, 1); });
     } else {  // one wavefront per listed instance; a launch of at most 16 instances repeats failed sweeps (sweeps_width of ltompc.hip)
       const int ms = n_launch <= 16 ? 4 : 1;
-      if (PI) wave64_lds("k_riccati1_pi", n_launch, ric1_lds_bytes(N), [&] { k_riccati1_pi(K, Wpi, la, it, ms); });
+      if (ric1q) {  // four wavefronts per listed instance, dynamic LDS of exactly ric1q_lds_bytes(N)
+        if (PI) wg("k_riccati1q_pi", n_launch, 256, ric1q_lds_bytes(N), LtWave::STACK, [&] { k_riccati1q_pi(K, Wpi, la, it, ms); });
+        else wg("k_riccati1q", n_launch, 256, ric1q_lds_bytes(N), LtWave::STACK, [&] { k_riccati1q(K, W, la, it, ms); });
+      } else if (PI) wave64_lds("k_riccati1_pi", n_launch, ric1_lds_bytes(N), [&] { k_riccati1_pi(K, Wpi, la, it, ms); });
       else wave64_lds("k_riccati1", n_launch, ric1_lds_bytes(N), [&] { k_riccati1(K, W, la, it, ms); });
     }
+  };
+  // the step selection: k_step1 with one workgroup of 320 lanes per listed instance, or the separate launches
+  const auto run_step = [&] {
+    if (step1) {
+      if (PI) wg("k_step1_pi", n_launch, 320, 0, LtWave::STACK, [&] { ref ? k_step1_pi<BoundsRef>(&K, &Wpi, la) : k_step1_pi<BoundsAny>(&K, &Wpi, la); });
+      else wg("k_step1", n_launch, 320, 0, LtWave::STACK, [&] { el ? (ref ? k_step1<BoundsRef, true>(&K, &W, la) : k_step1<BoundsAny, true>(&K, &W, la)) : (ref ? k_step1<BoundsRef, false>(&K, &W, la) : k_step1<BoundsAny, false>(&K, &W, la)); });
+      return;
+    }
+    run_linesearch(0, Bp, N * Bp);
+    run_pick(0, Bp);
+    if (K.o.n_linesearch > 1 && W.ls_count[0] > 0) {
+      const int jw = W.ls_count[0];
+      run_linesearch(1, jw, (K.o.n_linesearch - 1) * N * jw);
+      run_pick(1, jw);
+    }
+    grid64(N * Bp, [&] { k_update(&K, &W, la); });
+  };
+  const auto identity_list = [&] {
+    for (int b = 0; b < Bp; b++) d_actl[0][b] = b;
+    d_nactl[0][0] = B, set_list(0, B);
+  };
+  // k_compact on the flags `done` (SI_DONE in a solve, SI_FINAL in the rollout): the other list becomes the current one
+  const auto compact_by_kernel = [&](const int* done, const int n_new) {
+    scan1024("k_compact", [&] { k_compact(d_actl[cur], d_nactl[cur], done, d_actl[cur ^ 1], d_nactl[cur ^ 1]); });
+    set_list(cur ^ 1, n_new);
   };
   std::vector<double> x(x0), u0((size_t)2 * B, 0.0), xn((size_t)8 * B);
   // k_plant_sens' planes (psn_prepare / psn_launch of deriv_passes.h): a work plane set, at the rows in effect
@@ -477,9 +643,66 @@ int main(int argc, char** argv) {
     for (size_t q = 0; q < cnt; q++) o[q] = v[q];
     put(o.data(), cnt);
   };
+  // final=1: what the run leaves behind, per slot (= the caller's instance: the rollout never packs, pack=1 has un-packed):
+  // status, iterations, x0[8], u_prev[2], the last node X_N[8], U_0[2], E0, orig, the state after the last plant step, and in
+  // the last column the number of re-packings of the run
+  const auto print_final = [&] {
+    printf("tick final\n");
+    for (int b = 0; b < B; b++) {
+      printf("%d %d %d", b, W.si[(size_t)SI_STATUS * Bp + b], W.si[(size_t)SI_ITERS * Bp + b]);
+      for (int i = 0; i < 8; i++) printf(" %.17g", W.x0[(size_t)i * Bp + b]);
+      for (int i = 0; i < 2; i++) printf(" %.17g", W.uprev[(size_t)i * Bp + b]);
+      for (int i = 0; i < 8; i++) printf(" %.17g", W.X[((size_t)i * (N + 1) + N) * Bp + b]);
+      for (int i = 0; i < 2; i++) printf(" %.17g", W.U[((size_t)i * N + 0) * Bp + b]);
+      printf(" %.17g %d", W.st[(size_t)ST_E0 * Bp + b], d_orig[b]);
+      for (int i = 0; i < 8; i++) printf(" %.17g", x[(size_t)8 * b + i]);
+      printf(" %d\n", n_packs);
+    }
+  };
+  if (rollout > 0) {
+    // ltompc_rollout_dev's loop on one stream, without events: k_roll_begin, then per pass k_roll_mark, k_roll_init, the iteration,
+    // k_roll_finish, k_roll_plant on the pass's list (the library runs it on another stream, beside the next pass), and k_compact
+    // on SI_FINAL by the library's rule.  The logs per tick in the columns of the synchronous run (instance, status, iterations, u0).
+    if (eval8 || K.o.warm_shift || derivs) return fprintf(stderr, "harness: rollout with eval=slot, without warm_shift and derivs (as the library)\n"), 2;
+    const int T = rollout;
+    double* x_rm = (double*)malloc(sizeof(double) * 8 * B);  // exact size
+    memcpy(x_rm, x.data(), sizeof(double) * 8 * B);
+    double* u_log = poisoned((size_t)2 * T * B);
+    int *st_log = ipoisoned((size_t)T * B, -1), *it_log = ipoisoned((size_t)T * B, -1), *cnt = ipoisoned(2, 0), *plist = ipoisoned(bp, -1);
+    grid64(B, [&] { k_roll_begin(W, T); });
+    grid64(B, [&] { k_zero_uprev(W); });
+    W.ls_count[0] = W.ls_count[1] = 0;
+    identity_list();
+    const Consts Kc = K;
+    const long long it_cap = (long long)T * ((long long)K.o.max_iter + 8) + 64;
+    for (long long it = 0;; it++) {
+      const int first = it == 0;
+      cnt[0] = cnt[1] = 0;
+      grid64(B, [&] { k_roll_mark(W, x_rm, K.o.resto_sticky, first); });
+      if (PI) grid64(N * Bp, [&] { k_roll_init_pi(&K, &Wpi, la, first); });
+      else grid64(N * Bp, [&] { k_roll_init(&K, &W, la, first); });
+      la.force_eval = 0;
+      run_eval(), run_riccati(-1), run_expand(), run_step();
+      grid64(Bp, [&] { k_roll_finish(W, la, u_log, st_log, it_log, T, cnt, plist); });
+      if (PI) grid64(n_launch, [&] { k_roll_plant_pi(Kc, Wpi, x_rm, K.o.t_step, 100, cnt + 1, plist); });
+      else grid64(n_launch, [&] { k_roll_plant(Kc, W, x_rm, K.o.t_step, 100, cnt + 1, plist); });
+      const int n_left = cnt[0];  // instances that still had ticks to do (counted before this pass's plant steps)
+      if (n_left == 0) break;
+      if (it >= it_cap) return fprintf(stderr, "harness: rollout iteration cap reached\n"), 1;
+      if (n_left <= (pack_num * n_launch) / 8) compact_by_kernel(W.si + (size_t)SI_FINAL * Bp, n_left);
+    }
+    for (int t = 0; t < T; t++) {
+      printf("tick %d\n", t);
+      for (int b = 0; b < B; b++)
+        printf("%d %d %d %.17g %.17g\n", b, st_log[(size_t)b * T + t], it_log[(size_t)b * T + t], u_log[((size_t)b * T + t) * 2], u_log[((size_t)b * T + t) * 2 + 1]);
+    }
+    memcpy(x.data(), x_rm, sizeof(double) * 8 * B);
+    if (final_block) print_final();
+    return 0;
+  }
   for (int tick = 0; tick < ticks; tick++) {
     const int cold = tick == 0;
-    grid64(B, [&] { k_load_x0(W, x.data(), nullptr, K.o.resto_sticky, cold ? 0 : 1); });
+    grid64(B, [&] { k_load_x0(W, x.data(), packed ? d_orig : nullptr, K.o.resto_sticky, cold ? 0 : 1); });  // (the packed order is kept between ticks)
     if (cold) grid64(B, [&] { k_zero_uprev(W); });
     if (!cold && K.o.warm_shift) {
       grid64((N + 1) * Bp, [&] { k_shift(W, 0); });
@@ -488,37 +711,54 @@ int main(int argc, char** argv) {
     if (PI) grid64(N * Bp, [&] { k_init_pi(&K, &Wpi, cold); });
     else grid64(N * Bp, [&] { k_init(&K, &W, cold); });
     memset(W.active, 0, sizeof(int) * (K.o.max_iter + 2)), W.ls_count[0] = W.ls_count[1] = 0;
-    for (int b = 0; b < Bp; b++) d_act[b] = b;
-    d_nact[0] = B, n_launch = B;
+    identity_list();
+    bool force_eval_next = false;
     for (int it = 0;; it++) {
+      la.force_eval = force_eval_next ? 1 : 0, force_eval_next = false;
       run_eval();
       run_riccati(it);
       if (it >= K.o.max_iter) break;
       run_expand();
-      run_linesearch(0, Bp, N * Bp);
-      run_pick(0, Bp);
-      if (K.o.n_linesearch > 1 && W.ls_count[0] > 0) {
-        const int jw = W.ls_count[0];
-        run_linesearch(1, jw, (K.o.n_linesearch - 1) * N * jw);
-        run_pick(1, jw);
-      }
-      grid64(N * Bp, [&] { k_update(&K, &W, la); });
+      run_step();
       int left = 0;
       for (int b = 0; b < B; b++) left += !W.si[(size_t)SI_DONE * Bp + b];
       if (!left) break;
-      if (compact) {  // stable compaction of the unfinished instances of the current list; the rest of the list keeps -1
+      int* const done = W.si + (size_t)SI_DONE * Bp;
+      if (pack) {  // the library's rule (ltompc_make_step_dev), with the width above which instances are moved as an argument
+        if (left > (pack_num * n_launch) / 8) continue;
+        if (n_launch > pack_min) {
+          if (!packed) grid64(B, [&] { k_act_identity(d_orig, d_perm, B); });
+          packed = true, n_packs++;
+          scan1024("k_pack_perm", [&] { k_pack_perm(d_nactl[cur], done, d_perm, d_actl[cur ^ 1], d_nactl[cur ^ 1]); });
+          for (int pass = 0; pass < 2; pass++)
+            grid_bs((size_t)(N + 1) * n_launch, 256, [&] { k_pack(W, d_perm, d_nactl[cur], n_launch, d_orig, ni, (int)nel, pass); });
+          force_eval_next = true;
+          set_list(cur ^ 1, left);
+        } else compact_by_kernel(done, left);
+      } else if (compact_kernel) {
+        compact_by_kernel(done, left);
+      } else if (compact) {  // stable compaction of the unfinished instances of the current list; the rest of the list keeps -1
+        int* const d_act = d_actl[cur];
         int n = 0;
-        for (int j = 0; j < d_nact[0]; j++)
+        for (int j = 0; j < d_nactl[cur][0]; j++)
           if (!W.si[(size_t)SI_DONE * Bp + d_act[j]]) d_act[n++] = d_act[j];
         for (int j = n; j < Bp; j++) d_act[j] = -1;
-        d_nact[0] = n, n_launch = n;
+        d_nactl[cur][0] = n, n_launch = n;
       }
     }
-    if (derivs) grid64(B, [&] { k_psens_keep_uprev(W, uprev_rm, nullptr); });  // (before k_store_u0 makes W.uprev its u0)
-    grid64(B, [&] { k_store_u0(W, u0.data(), nullptr); });
+    if (derivs) grid64(B, [&] { k_psens_keep_uprev(W, uprev_rm, packed ? d_orig : nullptr); });  // (before k_store_u0 makes W.uprev its u0)
+    grid64(B, [&] { k_store_u0(W, u0.data(), packed ? d_orig : nullptr); });
+    if (pack && packed && tick == ticks - 1) {  // ensure_unpacked (ltompc.hip): slot j goes back to orig[j]
+      grid64(B, [&] { k_pack_inverse(d_orig, d_perm, B); });
+      for (int pass = 0; pass < 2; pass++)
+        grid_bs((size_t)(N + 1) * B, 256, [&] { k_pack(W, d_perm, nullptr, B, d_orig, ni, (int)nel, pass); });
+      packed = false;
+    }
     printf("tick %d\n", tick);
-    for (int b = 0; b < B; b++)
-      printf("%d %d %d %.17g %.17g %.17g %d %d %d %.17g %.17g\n", b, W.si[(size_t)SI_STATUS * Bp + b], W.si[(size_t)SI_ITERS * Bp + b], u0[2 * b], u0[2 * b + 1],
+    std::vector<int> slot_of(B);  // the slot of the caller's instance r (identity unless packed)
+    for (int b = 0; b < B; b++) slot_of[d_orig[b]] = b;
+    for (int r = 0, b = 0; r < B && (b = slot_of[r], true); r++)
+      printf("%d %d %d %.17g %.17g %.17g %d %d %d %.17g %.17g\n", r, W.si[(size_t)SI_STATUS * Bp + b], W.si[(size_t)SI_ITERS * Bp + b], u0[2 * r], u0[2 * r + 1],
              W.st[(size_t)ST_E0 * Bp + b], W.si[(size_t)SI_NRESTO * Bp + b], W.si[(size_t)SI_NSHIFT * Bp + b], W.si[(size_t)SI_NFALLBACK * Bp + b],
              W.st[(size_t)ST_VIOL * Bp + b], W.st[(size_t)ST_G0 * Bp + b]);
     if (derivs) {
@@ -578,6 +818,7 @@ int main(int argc, char** argv) {
     else grid64(B, [&] { k_plant(Kc, B, x.data(), u0.data(), K.o.t_step, 100, xn.data()); });
     x = xn;
   }
+  if (final_block) print_final();
   if (dump) fclose(dump);
   return 0;
 }

@@ -8,8 +8,12 @@
 //     k_plant, k_test_model, k_sens_eval, k_psens_cond, k_plant_sens, ...);
 //   - the one-wavefront kernels on the lock-step wavefront below (k_riccati8, k_riccati1, k_eval8, k_expand8, k_pick,
 //     k_sens_eval8, k_sens_riccati8, k_sens_forward, k_psens_sweep, k_adj_sweep and their _pi forms).
-// What does not: kernels whose workgroup has several wavefronts (k_riccati1q, k_step1, the packing kernels k_compact / k_pack*,
-// the rollout kernels).  They are compiled against this file and never called; __syncthreads() stays a placeholder.
+//   - the kernels whose workgroup has several wavefronts on the lock-step workgroup (LtWave::run): k_riccati1q (4 wavefronts,
+//     WG_SYNC_LDS), k_step1 (5, __syncthreads), k_compact / k_pack_perm (16, a scan in LDS), and their _pi forms.  Its wavefronts
+//     run one after the other between two workgroup barriers, in ascending or in descending order (LtWave::desc_waves); the tests
+//     make every such run in both orders and compare the results bit for bit, which is how a missing barrier shows.
+// What it cannot model: several lanes adding to ONE LDS word in the same instruction (below); the ordering of global memory
+// BETWEEN workgroups (the blocks of a launch run one after the other, each to its end); concurrent streams.
 //
 // The lock-step wavefront: 64 lanes as 64 cooperative fibers on one OS thread.  A lane runs until it reaches a collective
 // (__shfl, __shfl_xor, __any, WAVE_SYNC, grp_*) or returns; when every lane has stopped, the scheduler checks that all lanes of
@@ -22,19 +26,29 @@
 //     collectives: the hardware executes a shuffle under the EXEC mask, and a lane group that is alone in a branch (k_pick:
 //     `if (!live) return` per instance, the line search's per-instance candidate loop) reads only lanes of its own group, all of
 //     them active.
-//   - WAVE_SYNC is wave-level while the wave agrees and falls back to the instance groups in diverged control flow (see run()).
+//   - WAVE_SYNC is wave-level while the wave agrees and falls back to the instance groups in diverged control flow (see advance()).
 // Between two collectives the lanes run one after the other in DESCENDING order, so a lane with i = 0 (lanes 0..7), the lane
 // that writes an instance's scalars in the kernels, runs after the lanes that have read them "in the same instruction" on the
 // device.  The order is fixed: every run of the harness takes the same path.  What this cannot model is several lanes adding to
 // ONE LDS word in the same instruction (on the device each reads the old value and stores the same new one): lin8 (eval8.h)
 // does that through the model functions and has a harness branch for it.
 //
+// The lock-step workgroup: W wavefronts of 64 lanes, threadIdx.x = 0 .. 64 W - 1, all fibers of the one OS thread.  The
+// collectives above act within each wavefront.  __syncthreads() and WG_SYNC_LDS() (riccati.h) are workgroup collectives: a
+// barrier completes when every lane of the workgroup has returned from the kernel or stands at the same barrier site; lanes at
+// different barrier sites, or lanes at a barrier while others wait at a wave-level collective that cannot complete, end the run
+// with the same report.  Between two barriers each wavefront runs as far as it can before the next one starts, in ascending or
+// in descending wavefront order (see run()).
+//
 // __shared__ is `static`: one object per program, which is one object per workgroup while the blocks of a launch run one after
-// the other (they do).  The dynamic LDS of k_riccati1 is lt_dyn_lds, set by the harness per block (exact size, NaN-filled).
+// the other (they do).  The dynamic LDS of k_riccati1 / k_riccati1q is lt_dyn_lds, set by the harness per block (exact size,
+// NaN-filled).
 #pragma once
 // The harness branches of csrc/ that need the lock-step wavefront (WAVE_SYNC as a collective, lt_dyn_lds, lin8's private copies)
 // ask for this; with a shim that does not define it they compile as inert placeholders, as before there was a wavefront.
 #define LTOMPC_HARNESS_WAVEFRONT 1
+// ... and those that need workgroups of several wavefronts (WG_SYNC_LDS as a workgroup barrier, k_riccati1q's dynamic LDS) for this
+#define LTOMPC_HARNESS_WORKGROUP 1
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -58,7 +72,6 @@ template <class T, class V>
 inline T atomicAdd(T* p, V v) { return __atomic_fetch_add(p, (T)v, __ATOMIC_RELAXED); }
 inline long long clock64() { return 0; }
 inline int min(int a, int b) { return a < b ? a : b; }
-inline void __syncthreads() {}  // placeholder (multi-wave workgroups are not run)
 inline void __threadfence() {}
 #define __builtin_amdgcn_fence(a, b) ((void)0)
 #define __builtin_amdgcn_wave_barrier() ((void)0)
@@ -110,24 +123,34 @@ lt_switch:
 )");
 
 struct LtWave {
-  enum { READY = 0, AT_WAVE, AT_GROUP, DONE };
-  static constexpr int NL = 64;
-  static constexpr size_t STACK = (size_t)1 << 20;
+  enum { READY = 0, AT_WAVE, AT_GROUP, AT_BARRIER, DONE };
+  static constexpr int NL = 64;     // lanes of a wavefront
+  static constexpr int MAXW = 16;   // wavefronts of a workgroup (1024 threads)
+  static constexpr int MAXL = NL * MAXW;
+  // Stacks: allocated when a lane first runs, at the size the launch asks for.  1 MiB for the solver's kernels (model derivatives
+  // with their sanitizer frames); the 1024-lane scan kernels (k_compact, k_pack_perm: a handful of ints per lane) ask for
+  // STACK_SMALL, so that their 1024 fibers take 64 MiB of address space instead of 1 GiB.  A word at the low end of every stack is
+  // checked whenever its lane stops: a lane that needs more ends the run instead of writing into its neighbour.
+  static constexpr size_t STACK = (size_t)1 << 20, STACK_SMALL = (size_t)64 << 10;
+  static constexpr uint64_t CANARY = 0x5AFE57ACC0FFEE11ull;
   struct Lane {
     void* sp = nullptr;
     char* stack = nullptr;
+    size_t stack_size = 0;
     void* fake = nullptr;
     int state = DONE;
     const char *what = "", *file = "";
     int line = 0;
     uint64_t put = 0;
   };
-  Lane lane[NL];
-  uint64_t got[NL];  // the values of the collective a lane has just been released from
+  Lane lane[MAXL];
+  uint64_t got[MAXL];  // the values of the collective a lane has just been released from
   void* sched_sp = nullptr;
   const void* sched_bottom = nullptr;
   size_t sched_size = 0;
   int cur = -1;
+  int nw = 1;               // wavefronts of the workgroup that runs
+  bool desc_waves = false;  // wave_order=desc: between two barriers the wavefronts run from the last to the first
   void (*body)(void*) = nullptr;
   void* arg = nullptr;
   const char* kernel = "";
@@ -146,88 +169,140 @@ struct LtWave {
     lt_switch(&l.sp, w.sched_sp);
     abort();
   }
+  bool same_place(const int a, const int c) const { return lane[c].state == lane[a].state && lane[c].line == lane[a].line && !strcmp(lane[c].file, lane[a].file); }
   [[noreturn]] void report(const char* why) {
+    const int n = nw * NL;
     fprintf(stderr, "lock-step wavefront: MISMATCHED COLLECTIVE in %s, block %u: %s\n", kernel, blockIdx.x, why);
-    for (int a = 0; a < NL; a++) {  // lanes grouped by where they stand
+    for (int a = 0; a < n; a++) {  // lanes grouped by where they stand (lane = threadIdx.x; wavefront = lane / 64)
       bool first = true;
-      for (int c = 0; c < a; c++)
-        if (lane[c].state == lane[a].state && lane[c].line == lane[a].line && !strcmp(lane[c].file, lane[a].file)) first = false;
+      for (int c = 0; c < a && first; c++)
+        if (same_place(a, c)) first = false;
       if (!first) continue;
       if (lane[a].state == DONE) fprintf(stderr, "  returned from the kernel: lanes");
+      else if (lane[a].state == READY) fprintf(stderr, "  running: lanes");
       else fprintf(stderr, "  at %s, %s:%d: lanes", lane[a].what, lane[a].file, lane[a].line);
-      for (int c = a; c < NL; c++)
-        if (lane[c].state == lane[a].state && lane[c].line == lane[a].line && !strcmp(lane[c].file, lane[a].file)) fprintf(stderr, " %d", c);
+      for (int c = a; c < n; c++) {  // as ranges: a workgroup has up to 1024 lanes
+        if (!same_place(a, c)) continue;
+        int e = c;
+        while (e + 1 < n && same_place(a, e + 1)) e++;
+        if (e > c + 1) fprintf(stderr, " %d-%d", c, e);
+        else if (e > c) fprintf(stderr, " %d %d", c, e);
+        else fprintf(stderr, " %d", c);
+        c = e;
+      }
       fprintf(stderr, "\n");
     }
     fflush(stderr);
     _exit(3);
   }
   bool same_site(const int a, const int b) const { return lane[a].line == lane[b].line && !strcmp(lane[a].file, lane[b].file) && !strcmp(lane[a].what, lane[b].what); }
-  // one workgroup of one wavefront
-  void run(const char* name, void (*fn)(void*), void* a) {
+  // One wavefront (lanes base .. base + 63): its ready lanes run, in descending order, until each stops at a collective or returns;
+  // then the wave-level or group-level collectives of the wavefront that can complete do.  False when nothing moved.
+  bool advance(const int base) {
+    bool moved = false;
+    for (int l = base + NL - 1; l >= base; l--) {
+      if (lane[l].state != READY) continue;
+      cur = l, threadIdx.x = l;
+      void* fake = nullptr;
+      LT_FIBER_START(&fake, lane[l].stack, lane[l].stack_size);
+      lt_switch(&sched_sp, lane[l].sp);
+      LT_FIBER_FINISH(fake, nullptr, nullptr);
+      uint64_t canary;
+      memcpy(&canary, lane[l].stack, sizeof canary);
+      if (canary != CANARY) fprintf(stderr, "lock-step wavefront: lane %d of %s has run over its stack of %zu bytes\n", l, kernel, lane[l].stack_size), _exit(3);
+      moved = true;
+    }
+    cur = -1;
+    int n_wave = 0, n_group = 0;
+    for (int l = base; l < base + NL; l++) n_wave += lane[l].state == AT_WAVE, n_group += lane[l].state == AT_GROUP;
+    bool progress = false;
+    bool wave_agrees = n_wave == NL;
+    for (int l = base + 1; l < base + NL && wave_agrees; l++) wave_agrees = same_site(base, l);
+    if (wave_agrees) {
+      for (int l = base; l < base + NL; l++) got[l] = lane[l].put, lane[l].state = READY;
+      progress = true;
+    } else if (n_group) {
+      for (int g = base; g < base + 8; g++) {
+        int n = 0;
+        for (int i = 0; i < 8; i++) n += lane[g + 8 * i].state == AT_GROUP;
+        if (n < 8) continue;
+        for (int i = 1; i < 8; i++)
+          if (!same_site(g, g + 8 * i)) report("the lanes of an instance group stand at different grp_* collectives");
+        for (int i = 0; i < 8; i++) got[g + 8 * i] = lane[g + 8 * i].put, lane[g + 8 * i].state = READY;
+        progress = true;
+      }
+    }
+    if (!progress && n_wave) {
+      // WAVE_SYNC in diverged control flow.  Unlike a shuffle or a vote it is legal there: on the device it is two fences and
+      // a scheduling barrier, no instruction that waits for other lanes.  d_eval8 has one inside `if (reinit)`, a branch that
+      // the lane groups of some instances take and others do not (it orders lane 0's stores of the re-initialised slot before
+      // the loads of the slot's other lanes), and k_eval8's groups exchange through their own LDS slot only.  So when the wave
+      // cannot agree, a WAVE_SYNC completes for every instance group whose eight lanes stand at the same site, like a grp_*;
+      // the groups then run one collective apart and a group may return while another still works.  Shuffles and votes stay
+      // strict, and so does a group whose own lanes disagree or have partly returned.
+      for (int g = base; g < base + 8; g++) {
+        bool all = true;
+        for (int i = 0; i < 8 && all; i++) all = lane[g + 8 * i].state == AT_WAVE && !strcmp(lane[g + 8 * i].what, "WAVE_SYNC") && same_site(g, g + 8 * i);
+        if (!all) continue;
+        for (int i = 0; i < 8; i++) got[g + 8 * i] = 0, lane[g + 8 * i].state = READY;
+        progress = true;
+      }
+    }
+    return moved || progress;
+  }
+  // One workgroup of n_waves wavefronts (threadIdx.x = 0 .. 64 n_waves - 1).  Every wavefront runs as far as it can, through its
+  // own wave-level and group-level collectives, until each of its lanes has returned or waits at a workgroup barrier
+  // (__syncthreads, WG_SYNC_LDS); the wavefronts do so ONE AFTER THE OTHER, in ascending order or (desc_waves) in descending
+  // order.  A barrier completes when every lane of the workgroup has returned or stands at the same barrier site.  What a
+  // wavefront writes before a barrier, another reads after it in both orders; without the barrier one order reads the old word
+  // and the other the new one, so a run whose printed values differ between the two orders has a missing barrier (which no
+  // sanitizer sees).  Within a wavefront the order stays what it was, descending lanes (see the top of the file): the lanes of
+  // a wavefront execute an instruction together, so their order stands for nothing the hardware could do differently.
+  void run(const char* name, const int n_waves, const size_t stack_bytes, void (*fn)(void*), void* a) {
     if (cur >= 0) fprintf(stderr, "lock-step wavefront: launch from inside a kernel\n"), _exit(3);
-    kernel = name, body = fn, arg = a;
-    for (int l = 0; l < NL; l++) {
+    if (n_waves < 1 || n_waves > MAXW) fprintf(stderr, "lock-step wavefront: a workgroup of %d wavefronts\n", n_waves), _exit(3);
+    kernel = name, body = fn, arg = a, nw = n_waves;
+    const int n = nw * NL;
+    for (int l = 0; l < n; l++) {
       Lane& L = lane[l];
-      if (!L.stack) L.stack = (char*)malloc(STACK);
+      if (L.stack_size < stack_bytes) free(L.stack), L.stack = (char*)malloc(stack_bytes), L.stack_size = stack_bytes;
+      memcpy(L.stack, &CANARY, sizeof CANARY);
       // a fresh stack: six zeroed callee-saved registers, then entry() as the return address of lt_switch, then entry()'s own (null)
-      void** top = (void**)(((uintptr_t)L.stack + STACK) & ~(uintptr_t)15);
+      void** top = (void**)(((uintptr_t)L.stack + L.stack_size) & ~(uintptr_t)15);
       top[-1] = nullptr, top[-2] = (void*)&entry;
       for (int q = 3; q <= 8; q++) top[-q] = nullptr;
       L.sp = top - 8;
       L.state = READY, L.what = L.file = "", L.line = 0, L.fake = nullptr;
     }
     for (;;) {
-      for (int l = NL - 1; l >= 0; l--) {
-        if (lane[l].state != READY) continue;
-        cur = l, threadIdx.x = l;
-        void* fake = nullptr;
-        LT_FIBER_START(&fake, lane[l].stack, STACK);
-        lt_switch(&sched_sp, lane[l].sp);
-        LT_FIBER_FINISH(fake, nullptr, nullptr);
+      for (int q = 0; q < nw; q++) {
+        const int base = (desc_waves ? nw - 1 - q : q) * NL;
+        while (advance(base)) {}
       }
-      cur = -1;
-      int n_wave = 0, n_done = 0, n_group = 0;
-      for (int l = 0; l < NL; l++) n_wave += lane[l].state == AT_WAVE, n_done += lane[l].state == DONE, n_group += lane[l].state == AT_GROUP;
-      if (n_done == NL) break;
-      bool progress = false;
-      bool wave_agrees = n_wave == NL;
-      for (int l = 1; l < NL && wave_agrees; l++) wave_agrees = same_site(0, l);
-      if (wave_agrees) {
-        for (int l = 0; l < NL; l++) got[l] = lane[l].put, lane[l].state = READY;
-        progress = true;
-      } else if (n_group) {
-        for (int g = 0; g < 8; g++) {
-          int n = 0;
-          for (int i = 0; i < 8; i++) n += lane[g + 8 * i].state == AT_GROUP;
-          if (n < 8) continue;
-          for (int i = 1; i < 8; i++)
-            if (!same_site(g, g + 8 * i)) report("the lanes of an instance group stand at different grp_* collectives");
-          for (int i = 0; i < 8; i++) got[g + 8 * i] = lane[g + 8 * i].put, lane[g + 8 * i].state = READY;
-          progress = true;
+      int n_done = 0, n_bar = 0, first = -1;
+      for (int l = 0; l < n; l++) {
+        n_done += lane[l].state == DONE;
+        if (lane[l].state == AT_BARRIER) n_bar++, first = first < 0 ? l : first;
+      }
+      if (n_done == n) break;
+      if (n_done + n_bar < n) {  // a wavefront is stuck at a wave-level or group-level collective
+        for (int w = 0; w < nw; w++) {
+          int s_wave = 0, s_done = 0, s_bar = 0;
+          for (int l = w * NL; l < (w + 1) * NL; l++) s_wave += lane[l].state == AT_WAVE, s_done += lane[l].state == DONE, s_bar += lane[l].state == AT_BARRIER;
+          if (s_done + s_bar == NL) continue;
+          if (s_wave == NL) report("the lanes stand at different wave-level collectives");
+          if (s_bar || n_bar) report("some lanes wait at a workgroup barrier while others wait at a wave-level collective that cannot complete");
+          report(s_done ? "some lanes wait at a collective that the others, having returned or waiting elsewhere, never reach"
+                        : "the lanes wait at collectives that cannot complete together");
         }
       }
-      if (!progress) {
-        // WAVE_SYNC in diverged control flow.  Unlike a shuffle or a vote it is legal there: on the device it is two fences and
-        // a scheduling barrier, no instruction that waits for other lanes.  d_eval8 has one inside `if (reinit)`, a branch that
-        // the lane groups of some instances take and others do not (it orders lane 0's stores of the re-initialised slot before
-        // the loads of the slot's other lanes), and k_eval8's groups exchange through their own LDS slot only.  So when the wave
-        // cannot agree, a WAVE_SYNC completes for every instance group whose eight lanes stand at the same site, like a grp_*;
-        // the groups then run one collective apart and a group may return while another still works.  Shuffles and votes stay
-        // strict, and so does a group whose own lanes disagree or have partly returned.
-        for (int g = 0; g < 8; g++) {
-          bool all = true;
-          for (int i = 0; i < 8 && all; i++) all = lane[g + 8 * i].state == AT_WAVE && !strcmp(lane[g + 8 * i].what, "WAVE_SYNC") && same_site(g, g + 8 * i);
-          if (!all) continue;
-          for (int i = 0; i < 8; i++) got[g + 8 * i] = 0, lane[g + 8 * i].state = READY;
-          progress = true;
-        }
-      }
-      if (!progress && n_wave == NL) report("the lanes stand at different wave-level collectives");
-      if (!progress) report(n_done ? "some lanes wait at a collective that the others, having returned or waiting elsewhere, never reach"
-                                   : "the lanes wait at collectives that cannot complete together");
+      for (int l = first; l < n; l++)
+        if (lane[l].state == AT_BARRIER && !same_site(first, l)) report("the lanes of the workgroup stand at different barriers");
+      for (int l = first; l < n; l++)
+        if (lane[l].state == AT_BARRIER) got[l] = 0, lane[l].state = READY;
     }
   }
+  void run(const char* name, void (*fn)(void*), void* a) { run(name, 1, STACK, fn, a); }  // one workgroup of one wavefront
   // called by a lane: stop at a collective, come back with got[] filled
   void collective(const int level, const char* what, const char* file, const int line, const uint64_t v) {
     if (cur < 0) fprintf(stderr, "lock-step wavefront: %s at %s:%d outside a wavefront launch\n", what, file, line), _exit(3);
@@ -254,7 +329,7 @@ template <class T> inline T lt_shfl(const T v, const int src, const char* file, 
   LtWave& w = LtWave::self();
   w.collective(LtWave::AT_WAVE, "__shfl", file, line, lt_bits(v));
   if (src < 0 || src >= LtWave::NL) fprintf(stderr, "lock-step wavefront: __shfl from lane %d at %s:%d\n", src, file, line), _exit(3);
-  return lt_unbits<T>(w.got[src]);
+  return lt_unbits<T>(w.got[(w.cur & ~(LtWave::NL - 1)) + src]);
 }
 template <class T> inline T lt_shfl_xor(const T v, const int mask, const char* file, const int line) {
   LtWave& w = LtWave::self();
@@ -266,10 +341,12 @@ inline int lt_any(const int p, const char* file, const int line) {
   LtWave& w = LtWave::self();
   w.collective(LtWave::AT_WAVE, "__any", file, line, p ? 1 : 0);
   int r = 0;
-  for (int l = 0; l < LtWave::NL; l++) r |= w.got[l] != 0;
+  for (int l = 0; l < LtWave::NL; l++) r |= w.got[(w.cur & ~(LtWave::NL - 1)) + l] != 0;
   return r;
 }
 inline void lt_wave_sync(const char* file, const int line) { LtWave::self().collective(LtWave::AT_WAVE, "WAVE_SYNC", file, line, 0); }
+// workgroup barriers: __syncthreads() and WG_SYNC_LDS() (riccati.h)
+inline void lt_barrier(const char* what, const char* file, const int line) { LtWave::self().collective(LtWave::AT_BARRIER, what, file, line, 0); }
 // one xor-shuffle among the eight lanes that share g = lane & 7 (x = 8, 16, 32)
 inline double lt_grp_xchg(const double v, const int x, const char* what, const char* file, const int line) {
   LtWave& w = LtWave::self();
@@ -293,6 +370,7 @@ inline double lt_grp_min(double v, const char* file, const int line) {
   return v;
 }
 #undef LT_X
+#define __syncthreads() lt_barrier("__syncthreads", __FILE__, __LINE__)
 #define __shfl(v, src) lt_shfl((v), (src), __FILE__, __LINE__)
 #define __shfl_xor(v, mask) lt_shfl_xor((v), (mask), __FILE__, __LINE__)
 #define __any(p) lt_any((p), __FILE__, __LINE__)

@@ -7,8 +7,10 @@ kernel (the LTOMPC_RICCATI=serial path) and k_pick on the harness's lock-step wa
 same fixture: the wave kernels k_riccati8, k_riccati1, k_eval8 / k_expand8, k_sens_eval8, k_sens_riccati8, k_sens_forward,
 k_psens_sweep, k_adj_sweep, the thread-per-slot kernels of the derivative passes (k_sens_eval, k_psens_cond, k_plant_sens,
 k_planes_rows, k_loop_begin, k_loop_accum, k_theta_rows, k_slip_forces, k_test_ellipse, k_velocity_profile) and every _pi form.
-Still left out, because their workgroups have several wavefronts: k_riccati1q, k_step1, the packing kernels k_compact / k_pack*,
-the rollout kernels.
+test_host_harness_multiwave.py: the kernels whose workgroups have several wavefronts (k_riccati1q, k_step1, k_compact,
+k_pack_perm), k_pack / k_pack_inverse and the rollout kernels, every multi-wavefront run in both wavefront orders.
+Not modelled by the harness: several lanes adding to one LDS word in the same instruction, the ordering of global memory between
+workgroups, the rollout's two streams.
 
 The numbers are compared with the oracle (the GPU library's own results are compared with the oracle in test_gpu_parity.py).
 Test infrastructure only: the package never builds or loads this."""

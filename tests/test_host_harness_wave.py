@@ -8,6 +8,8 @@ Shapes: B = 9 (the first wavefront of k_riccati8 is full, the second holds one i
 the 64 slots of Bp are never written) and N in {2, 8} (2: the shortest horizon at which a stage has a successor to prefetch).
 The numbers are compared with the oracle, as in test_host_harness.py, and bit for bit between the kernel paths, as the GPU suite
 does (test_compaction_and_serial_riccati_do_not_change_results, test_interleaved_groups_match_uniform_handles).
+The kernels whose workgroups have several wavefronts (k_riccati1q, k_step1, k_compact / k_pack*) and the rollout kernels run in
+test_host_harness_multiwave.py, which imports this file's batch and helpers.
 Test infrastructure only: the package never builds or loads the harness."""
 import os
 
