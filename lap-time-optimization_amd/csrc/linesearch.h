@@ -160,70 +160,128 @@ __global__ void __launch_bounds__(64) k_linesearch_pi(const Consts* __restrict__
 // 8 lanes per instance (lane = g + 8 i, all 8 lanes of a group call this together): lane i reduces the stage partials
 // k = i, i+8, ...; the 8 lanes then hold the same numbers and take the same decisions, lane i == 0 writes.  (Keeps the
 // latency of this small step at N/8 dependent loads instead of N.)
+constexpr int PICK_Q = 5;  // stages per lane and round trip: N = 40 in one (with 8, k_step1's 256 registers do not hold the batch)
 template <bool PI = false>
 __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int b, const int i, const int phase,
                                        const bool append_list) {
   const int N = W.N;
   double* st = W.st;
   int* si = W.si;
-  if (STI(SI_DONE) || !STI(SI_STEP)) return;  // finished, or the Riccati sweep of this launch has to be repeated
   const ltompc_options& o = K.o;
-  const double mu = STD(ST_MU);
-  double a_pri = 1.0, a_dua = 1.0, gphid = 0.0;
-  // (loads of four stages in flight per round trip; the additions keep the order k = i, i + 8, ...)
-  for (int k0 = i; k0 < N; k0 += 32) {
-    double v[3][4];
+  // Everything the function can read on any of its paths, in ONE batch of loads: the per-instance state (the two flags that
+  // decide whether there is anything to do among them), x0 (eps switch only), the filter, the step partials and the measures
+  // of the current point and the full step.  The decisions are then taken in registers and lane i == 0 writes what changed in
+  // one group at the end: read and written field by field where it was used, the state cost a memory round trip per field
+  // (13 dependent ones on the common path; on gfx9 a load issued after a store waits for the store as well, vmcnt counts
+  // both in order).
+  int done = STI(SI_DONE), step = STI(SI_STEP);
+  double mu = STD(ST_MU), eps = STD(ST_EPS), eps_next = STD(ST_EPS_NEXT), force_reg = STD(ST_FORCE_REG), theta0 = STD(ST_THETA0);
+  double theta_max = STD(ST_THMAX), theta_min = STD(ST_THMIN), c00 = STD(ST_C00), rho = STD(ST_RHO);
+  int nfilt = STI(SI_NFILT), nlsfail = STI(SI_NLSFAIL), ntiny = STI(SI_NTINY), resto = STI(SI_RESTO), nresto = STI(SI_NRESTO);
+  int warm = STI(SI_WARM), nshift = STI(SI_NSHIFT), blowup = STI(SI_BLOWUP), iters = STI(SI_ITERS);
+  double x0[8];
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
+  for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
+  // the filter (at most FILTER_MAX pairs), in registers: it only changes when a candidate is accepted
+  double fth[FILTER_MAX], fph[FILTER_MAX];
+#pragma unroll
+  for (int f = 0; f < FILTER_MAX; f++) fth[f] = W.filt[(size_t)(2 * f) * W.Bp + b], fph[f] = W.filt[(size_t)(2 * f + 1) * W.Bp + b];
+  // horizon sums: lane i takes the stages k = i, i + 8, ...; PICK_Q of them per round trip (all of N <= 8 PICK_Q in the batch
+  // above), the additions keep the order k = i, i + 8, ...
+  double sp[3][PICK_Q], ls[6][PICK_Q];
+#pragma unroll
+  for (int q = 0; q < PICK_Q; q++) {
+    const int k = i + 8 * q < N ? i + 8 * q : N - 1;  // (past the horizon: a valid word, not used)
+    sp[0][q] = PL(W.SP, SP_apri, k, N), sp[1][q] = PL(W.SP, SP_adua, k, N), sp[2][q] = PL(W.SP, SP_gphid, k, N);
+#pragma unroll
+    for (int f = 0; f < 6; f++) ls[f][q] = PL(W.LS, f, k, N);  // candidates 0 (the current point) and 1 (the full step)
+  }
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (all of them in registers before the first use: left alone the compiler sinks the loads into the branches that use them)
+#define LT_PIN8(a) asm volatile("" : "+v"((a)[0]), "+v"((a)[1]), "+v"((a)[2]), "+v"((a)[3]), "+v"((a)[4]), "+v"((a)[5]), "+v"((a)[6]), "+v"((a)[7]))
+  asm volatile("" : "+v"(mu), "+v"(eps), "+v"(eps_next), "+v"(force_reg), "+v"(theta0), "+v"(theta_max), "+v"(theta_min), "+v"(c00), "+v"(rho));
+  asm volatile("" : "+v"(nfilt), "+v"(nlsfail), "+v"(ntiny), "+v"(resto), "+v"(nresto), "+v"(warm), "+v"(nshift), "+v"(blowup), "+v"(iters),
+                    "+v"(done), "+v"(step));
+  LT_PIN8(x0);
+  static_assert(FILTER_MAX % 8 == 0, "the filter is pinned in chunks of 8 pairs");
+#pragma unroll
+  for (int f = 0; f < FILTER_MAX; f += 8) LT_PIN8(fth + f);
+#pragma unroll
+  for (int f = 0; f < FILTER_MAX; f += 8) LT_PIN8(fph + f);
+#pragma unroll
+  for (int q = 0; q < PICK_Q; q++)
+    asm volatile("" : "+v"(sp[0][q]), "+v"(sp[1][q]), "+v"(sp[2][q]), "+v"(ls[0][q]), "+v"(ls[1][q]), "+v"(ls[2][q]), "+v"(ls[3][q]), "+v"(ls[4][q]), "+v"(ls[5][q]));
+#undef LT_PIN8
+#endif
+  if (done || !step) return;  // finished, or the Riccati sweep of this launch has to be repeated
+  double a_pri = 1.0, a_dua = 1.0, gphid = 0.0;
+#pragma unroll
+  for (int q = 0; q < PICK_Q; q++)
+    if (i + 8 * q < N) a_pri = fmin(a_pri, sp[0][q]), a_dua = fmin(a_dua, sp[1][q]), gphid += sp[2][q];
+  for (int k0 = i + 8 * PICK_Q; k0 < N; k0 += 8 * PICK_Q) {  // (N > 8 PICK_Q)
+    double v[3][PICK_Q];
+#pragma unroll
+    for (int q = 0; q < PICK_Q; q++) {
       const int k = k0 + 8 * q < N ? k0 + 8 * q : k0;
       v[0][q] = PL(W.SP, SP_apri, k, N), v[1][q] = PL(W.SP, SP_adua, k, N), v[2][q] = PL(W.SP, SP_gphid, k, N);
     }
 #pragma unroll
-    for (int q = 0; q < 4; q++)
+    for (int q = 0; q < PICK_Q; q++)
       if (k0 + 8 * q < N) a_pri = fmin(a_pri, v[0][q]), a_dua = fmin(a_dua, v[1][q]), gphid += v[2][q];
   }
   a_pri = grp_min(a_pri), a_dua = grp_min(a_dua), gphid = grp_sum(gphid);
-  // lterm(x_0) is a constant of the solve; kept so that phi matches the oracle's barrier objective
-  const double c00 = STD(ST_C00);
+  // c00 = lterm(x_0) is a constant of the solve; kept so that phi matches the oracle's barrier objective
   // filter measures of candidates lA and lB (sums over the horizon of the partials written by k_eval / k_linesearch): the
-  // loads of both go out together, a pair of candidates costs one round trip per 32 stages
-  auto measures2 = [&](int lA, int lB, double& thA, double& phA, double& thB, double& phB) {
-    double tA = 0.0, cA = 0.0, sA = 0.0, tB = 0.0, cB = 0.0, sB = 0.0;
-    for (int k0 = i; k0 < N; k0 += 32) {
-      double v[6][4];
+  // loads of both go out together, a pair of candidates costs one round trip per 8 PICK_Q stages
+  auto sums6 = [&](const int lA, const int lB, const int kbeg, double (&s)[6]) {  // adds the stages kbeg, kbeg + 8, ...
+    for (int k0 = kbeg; k0 < N; k0 += 8 * PICK_Q) {
+      double v[6][PICK_Q];
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
+      for (int q = 0; q < PICK_Q; q++) {
         const int k = k0 + 8 * q < N ? k0 + 8 * q : k0;
-        v[0][q] = PL(W.LS, 3 * lA + 0, k, N), v[1][q] = PL(W.LS, 3 * lA + 1, k, N), v[2][q] = PL(W.LS, 3 * lA + 2, k, N);
-        v[3][q] = PL(W.LS, 3 * lB + 0, k, N), v[4][q] = PL(W.LS, 3 * lB + 1, k, N), v[5][q] = PL(W.LS, 3 * lB + 2, k, N);
+#pragma unroll
+        for (int f = 0; f < 3; f++) v[f][q] = PL(W.LS, 3 * lA + f, k, N), v[3 + f][q] = PL(W.LS, 3 * lB + f, k, N);
       }
 #pragma unroll
-      for (int q = 0; q < 4; q++)
-        if (k0 + 8 * q < N) tA += v[0][q], cA += v[1][q], sA += v[2][q], tB += v[3][q], cB += v[4][q], sB += v[5][q];
+      for (int q = 0; q < PICK_Q; q++)
+        if (k0 + 8 * q < N) {
+#pragma unroll
+          for (int f = 0; f < 6; f++) s[f] += v[f][q];
+        }
     }
-    tA = grp_sum(tA), cA = grp_sum(cA), sA = grp_sum(sA), tB = grp_sum(tB), cB = grp_sum(cB), sB = grp_sum(sB);
-    thA = tA, phA = (c00 + cA) - mu * sA, thB = tB, phB = (c00 + cB) - mu * sB;
+  };
+  auto measures = [&](double (&s)[6], double& thA, double& phA, double& thB, double& phB) {
+#pragma unroll
+    for (int f = 0; f < 6; f++) s[f] = grp_sum(s[f]);
+    thA = s[0], phA = (c00 + s[1]) - mu * s[2], thB = s[3], phB = (c00 + s[4]) - mu * s[5];
   };
   double th0, ph0, th1, ph1;
-  measures2(0, 1, th0, ph0, th1, ph1);  // the current point and the full step
-  double theta0 = STD(ST_THETA0);
-  int nfilt = STI(SI_NFILT);
-  double theta_max = STD(ST_THMAX), theta_min = STD(ST_THMIN);
-  if (theta0 < 0.0) {
+  {  // the current point and the full step
+    double s[6] = {};
+#pragma unroll
+    for (int q = 0; q < PICK_Q; q++)
+      if (i + 8 * q < N) {
+#pragma unroll
+        for (int f = 0; f < 6; f++) s[f] += ls[f][q];
+      }
+    sums6(0, 1, i + 8 * PICK_Q, s);  // (N > 8 PICK_Q)
+    measures(s, th0, ph0, th1, ph1);
+  }
+  const bool th_init = theta0 < 0.0;  // first filter test since the filter was reset
+  if (th_init) {
     theta0 = th0, theta_max = 1e4 * fmax(1.0, theta0), theta_min = 1e-4 * fmax(1.0, theta0);
-    if (i == 0) STD(ST_THETA0) = theta0, STD(ST_THMAX) = theta_max, STD(ST_THMIN) = theta_min;
     nfilt = 0;
   }
   const double g_th = 1e-5, g_ph = 1e-8, eta_ph = 1e-8, s_th = 1.1, s_ph = 2.3, dlt = 1.0;
-  const double S = pen_scale(STD(ST_RHO)), iS = 1.0 / S;  // penalty scale (layout.h): the objective side of the tests in its units
+  const double S = pen_scale(rho), iS = 1.0 / S;  // penalty scale (layout.h): the objective side of the tests in its units
   bool accepted = false;
   double alpha = a_pri;
   const int n_ls = o.n_linesearch;
   const int n_try = (phase == 0) ? 1 : n_ls;  // phase 1 repeats the test of candidate 0 (same outcome) and goes on
-  // the filter (at most FILTER_MAX pairs) once, in registers: it only changes when a candidate is accepted
-  double fth[FILTER_MAX], fph[FILTER_MAX];
-#pragma unroll
-  for (int f = 0; f < FILTER_MAX; f++) fth[f] = W.filt[(size_t)(2 * f) * W.Bp + b], fph[f] = W.filt[(size_t)(2 * f + 1) * W.Bp + b];
+  // what the accepted candidate does to the filter in memory (written with the state at the end): drop the oldest pair,
+  // append one at position f_at
+  bool f_shift = false;
+  int f_at = -1;
   auto try_candidate = [&](const double th, const double ph) -> bool {  // true: accepted (filter updated)
     if (!isfinite(th) || !isfinite(ph) || th > theta_max) return false;
     bool in_filter = false;
@@ -236,19 +294,9 @@ __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int
     if (th0 <= theta_min && sw) ok = armijo;
     else ok = (th <= (1.0 - g_th) * th0) || (ph <= ph0 - g_ph * S * th0);
     if (!ok) return false;
-    if (!(sw && armijo)) {  // augment the filter (written by lane i == 0, nobody reads it again in this launch)
-      if (nfilt == FILTER_MAX) {
-        if (i == 0)
-          for (int f = 0; f + 1 < FILTER_MAX; f++) {
-            W.filt[(size_t)(2 * f) * W.Bp + b] = W.filt[(size_t)(2 * f + 2) * W.Bp + b];
-            W.filt[(size_t)(2 * f + 1) * W.Bp + b] = W.filt[(size_t)(2 * f + 3) * W.Bp + b];
-          }
-        nfilt--;
-      }
-      if (i == 0) {
-        W.filt[(size_t)(2 * nfilt) * W.Bp + b] = (1.0 - g_th) * th0;
-        W.filt[(size_t)(2 * nfilt + 1) * W.Bp + b] = ph0 - g_ph * S * th0;
-      }
+    if (!(sw && armijo)) {  // augment the filter (nobody reads it again in this launch)
+      if (nfilt == FILTER_MAX) f_shift = true, nfilt--;
+      f_at = nfilt;
       nfilt++;
     }
     return true;
@@ -258,7 +306,9 @@ __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int
   if (!accepted) alpha *= 0.5;
   for (int l = 1; l < n_try && !accepted; l += 2) {
     double thA, phA, thB, phB;
-    measures2(l + 1, l + 2 <= n_ls ? l + 2 : l + 1, thA, phA, thB, phB);
+    double s[6] = {};
+    sums6(l + 1, l + 2 <= n_ls ? l + 2 : l + 1, i, s);
+    measures(s, thA, phA, thB, phB);
     accepted = try_candidate(thA, phA);
     if (!accepted) {
       alpha *= 0.5;
@@ -269,43 +319,39 @@ __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int
     }
   }
   if (i != 0) return;  // one writer per instance from here on
-  if (phase == 0) {
-    STI(SI_LSMORE) = (!accepted && n_ls > 1) ? 1 : 0;
-    if (!accepted && n_ls > 1) {  // nothing has been modified yet: phase 1 decides
-      if (append_list) W.ls_list[atomicAdd(W.ls_count, 1)] = b;
-      return;
-    }
-  } else {
-    STI(SI_LSMORE) = 0;
+  if (phase == 0 && !accepted && n_ls > 1) {  // nothing has been modified yet: phase 1 decides
+    STI(SI_LSMORE) = 1;
+    if (th_init) STD(ST_THETA0) = theta0, STD(ST_THMAX) = theta_max, STD(ST_THMIN) = theta_min;
+    if (append_list) W.ls_list[atomicAdd(W.ls_count, 1)] = b;
+    return;
   }
   // Restoration phase (IPOPT enters its own when the filter line search fails): here an elastic mode, entered once per
   // solve on the first failed search or after stall_iter tiny steps.
-  const bool resto_ready = o.resto_rho > 0.0 && !(o.soft_rho > 0.0) && STI(SI_RESTO) == 0;
-  bool take = true, give_up = false, enter_resto = false;
+  const bool resto_ready = o.resto_rho > 0.0 && !(o.soft_rho > 0.0) && resto == 0;
+  bool take = true, give_up = false, enter_resto = false, stalled = false, shift = false;
+  bool th_reset = false;  // the filter restarts: theta0 = -1
   if (!accepted) {
-    const int nf = STI(SI_NLSFAIL) + 1;
-    STI(SI_NLSFAIL) = nf;
-    double fr = STD(ST_FORCE_REG);
+    nlsfail += 1;
+    const double fr = force_reg;
     if (resto_ready) {
       enter_resto = true, take = false;
-    } else if (o.max_ls_fail > 0 && nf >= o.max_ls_fail) {
+    } else if (o.max_ls_fail > 0 && nlsfail >= o.max_ls_fail) {
       give_up = true, take = false;
     } else if (fr < 1e4 * S) {
-      STD(ST_FORCE_REG) = fr == 0.0 ? 1e-2 * S : fr * 100.0;
+      force_reg = fr == 0.0 ? 1e-2 * S : fr * 100.0;
       take = false;
     } else {
       nfilt = 0;
       alpha = a_pri * pow(0.5, (double)(n_ls - 1));
     }
   }
-  if (give_up) STI(SI_STATUS) = LTOMPC_STATUS_STALLED, STI(SI_DONE) = 1;
+  if (give_up) stalled = true;
   if (take) {
-    STD(ST_FORCE_REG) = 0.0;
-    int nt = alpha <= 1e-3 ? STI(SI_NTINY) + 1 : 0;
-    STI(SI_NTINY) = nt;
-    if ((o.stall_iter > 0 && nt >= o.stall_iter) || (resto_ready && STI(SI_BLOWUP))) {  // (SI_BLOWUP: options.dual_inf_max, set by the head)
+    force_reg = 0.0;
+    ntiny = alpha <= 1e-3 ? ntiny + 1 : 0;
+    if ((o.stall_iter > 0 && ntiny >= o.stall_iter) || (resto_ready && blowup)) {  // (SI_BLOWUP: options.dual_inf_max, set by the head)
       if (resto_ready) enter_resto = true;
-      else STI(SI_STATUS) = LTOMPC_STATUS_STALLED, STI(SI_DONE) = 1;
+      else stalled = true;
       take = false;
     }
   }
@@ -317,34 +363,50 @@ __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int
     // slacks and multipliers (SI_REINIT).  The restoration phase proper follows if that start jams too:
     // the track constraints get elastic variables that cost resto_rho each; equality multipliers, slacks and the barrier
     // parameter start again at the current primal point.
-    const bool shift = o.resto_shift_retry && !o.warm_shift && STI(SI_WARM) && STI(SI_NSHIFT) == 0;
+    shift = o.resto_shift_retry && !o.warm_shift && warm && nshift == 0;
     double rho_new = 0.0;
-    if (shift) STI(SI_SHIFT) = 1, STI(SI_NSHIFT) = 1;
-    else STI(SI_RESTO) = 1, STI(SI_NRESTO) += 1, rho_new = o.resto_rho;
-    const double mu0 = o.mu_init * pen_scale(rho_new);
-    STI(SI_REINIT) = 1;
-    STD(ST_RHO) = rho_new, STD(ST_MU) = mu0;
-    STD(ST_EPS_NEXT) = (o.smooth_scale > 0 || o.smooth_eps_min > 0) ? fmax(o.smooth_eps_min, o.smooth_scale * o.mu_init) : 0.0;
-    if (STD(ST_EPS_NEXT) == STD(ST_EPS)) nfilt = 0, STD(ST_THETA0) = -1.0;  // (else: reset with the switch of the smoothing below)
-    STD(ST_DW_LAST) = 0.0, STD(ST_FORCE_REG) = 0.0;
-    STI(SI_NTINY) = 0, STI(SI_NACC) = 0, STI(SI_SINCEMU) = 0;
+    if (!shift) resto = 1, nresto += 1, rho_new = o.resto_rho;
+    rho = rho_new, mu = o.mu_init * pen_scale(rho_new);
+    eps_next = (o.smooth_scale > 0 || o.smooth_eps_min > 0) ? fmax(o.smooth_eps_min, o.smooth_scale * o.mu_init) : 0.0;
+    if (eps_next == eps) nfilt = 0, th_reset = true;  // (else: reset with the switch of the smoothing below)
+    force_reg = 0.0, ntiny = 0;
   }
+  if (!stalled) iters += 1;  // (a solve that stops here has completed `iters` iterations, like the oracle)
+  // table smoothing follows the barrier parameter with one iteration lag; the filter restarts when it changes
+  const bool eps_switched = eps_next != eps;
+  if (eps_switched) {
+    c00 = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps_next, x0, false, nullptr, nullptr);
+    nfilt = 0, th_reset = true;
+  }
+  // ---- the stores, in one group
+  STI(SI_LSMORE) = 0;
+  if (f_shift) {
+#pragma unroll
+    for (int f = 0; f + 1 < FILTER_MAX; f++) W.filt[(size_t)(2 * f) * W.Bp + b] = fth[f + 1], W.filt[(size_t)(2 * f + 1) * W.Bp + b] = fph[f + 1];
+  }
+  if (f_at >= 0) {
+    W.filt[(size_t)(2 * f_at) * W.Bp + b] = (1.0 - g_th) * th0;
+    W.filt[(size_t)(2 * f_at + 1) * W.Bp + b] = ph0 - g_ph * S * th0;
+  }
+  if (th_init) STD(ST_THMAX) = theta_max, STD(ST_THMIN) = theta_min;
+  if (th_init || th_reset) STD(ST_THETA0) = th_reset ? -1.0 : theta0;
+  if (!accepted) STI(SI_NLSFAIL) = nlsfail;
+  if (stalled) STI(SI_STATUS) = LTOMPC_STATUS_STALLED, STI(SI_DONE) = 1;
+  if (enter_resto) {
+    if (shift) STI(SI_SHIFT) = 1, STI(SI_NSHIFT) = 1;
+    else STI(SI_RESTO) = resto, STI(SI_NRESTO) = nresto;
+    STI(SI_REINIT) = 1;
+    STD(ST_RHO) = rho, STD(ST_MU) = mu;
+    STD(ST_EPS_NEXT) = eps_next;
+    STD(ST_DW_LAST) = 0.0;
+    STI(SI_NACC) = 0, STI(SI_SINCEMU) = 0;
+  }
+  STD(ST_FORCE_REG) = force_reg;
+  STI(SI_NTINY) = ntiny;
   STD(ST_ALPHA) = take ? alpha : 0.0, STD(ST_ADUA) = a_dua;
   STI(SI_STEP) = take ? 1 : 0;
-  if (!STI(SI_DONE)) STI(SI_ITERS) += 1;  // (a solve that stops here has completed `iters` iterations, like the oracle)
-  // table smoothing follows the barrier parameter with one iteration lag; the filter restarts when it changes
-  bool eps_switched = false;
-  if (STD(ST_EPS_NEXT) != STD(ST_EPS)) {
-    STD(ST_EPS) = STD(ST_EPS_NEXT);
-    {
-      double x0[8];
-#pragma unroll
-      for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
-      STD(ST_C00) = cost_eval(inst_params<PI>(K.p, W, b), K.T, STD(ST_EPS_NEXT), x0, false, nullptr, nullptr);
-    }
-    nfilt = 0, STD(ST_THETA0) = -1.0;
-    eps_switched = true;
-  }
+  STI(SI_ITERS) = iters;
+  if (eps_switched) STD(ST_EPS) = eps_next, STD(ST_C00) = c00;
   STI(SI_NFILT) = nfilt;
   STI(SI_SKIP_EVAL) = (!take && !eps_switched && !enter_resto) ? 1 : 0;  // the iterate did not move: the stage blocks stay valid
 }

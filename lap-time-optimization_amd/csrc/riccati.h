@@ -30,19 +30,19 @@ __device__ __forceinline__ int node0_rule(const ltompc_options& o, const double 
 // units of the penalty scale), filter and regularisation history dropped.  This launch does no sweep for the instance.
 // Used by the penalty escalation of the restoration phase and by the fallback of a tuned warm start; d_pick has the same
 // block for the entry of the restoration phase.
+// What it reads (ST_EPS, x0) comes in registers: d_head8 fetches them with the rest of the instance's state, so that no load
+// follows the head's stores.
 template <bool PI = false>
-__device__ __forceinline__ void restart_from_primal(const Consts& K, const Work& W, const int b, const double rho) {
+__device__ __forceinline__ void restart_from_primal(const Consts& K, const Work& W, const int b, const double rho, const double eps_now,
+                                                    const double (&x0)[8]) {
   double* st = W.st;
   int* si = W.si;
   const ltompc_options& o = K.o;
   const double mu0 = o.mu_init * pen_scale(rho);
   const double eps = (o.smooth_scale > 0 || o.smooth_eps_min > 0) ? fmax(o.smooth_eps_min, o.smooth_scale * o.mu_init) : 0.0;
   STD(ST_RHO) = rho, STD(ST_MU) = mu0, STD(ST_EPS_NEXT) = eps;
-  if (eps != STD(ST_EPS)) {  // (d_pick, which switches the smoothing otherwise, does not see the instance in this launch)
+  if (eps != eps_now) {  // (d_pick, which switches the smoothing otherwise, does not see the instance in this launch)
     STD(ST_EPS) = eps;
-    double x0[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
     STD(ST_C00) = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, x0, false, nullptr, nullptr);
   }
   STI(SI_REINIT) = 1;
@@ -50,6 +50,16 @@ __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work&
   STD(ST_DW_LAST) = 0.0, STD(ST_FORCE_REG) = 0.0;
   STI(SI_NTINY) = 0, STI(SI_NACC) = 0, STI(SI_SINCEMU) = 0;
   STI(SI_STEP) = 0, STI(SI_SKIP_EVAL) = 0;
+}
+
+// ... for a caller that has not fetched them (k_riccati)
+template <bool PI = false>
+__device__ __forceinline__ void restart_from_primal(const Consts& K, const Work& W, const int b, const double rho) {
+  double* st = W.st;
+  double x0[8];
+#pragma unroll
+  for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
+  restart_from_primal<PI>(K, W, b, rho, STD(ST_EPS), x0);
 }
 
 // ------------------------------------------------------------------------------------------ k_riccati
@@ -378,6 +388,8 @@ __global__ void __launch_bounds__(64) k_riccati(const Consts* __restrict__ Kp, c
 // (lane = g + 8 i) that own it in d_riccati8 / d_riccati1: lane i reduces the partials of the intervals k = i, i + 8, ...;
 // the sums over k are formed in the order k = 0..N-1 by every lane (identical to the serial kernel, so that all three
 // produce the same bits).  Returns false when no lane of the wavefront has a sweep to do.
+constexpr int HEAD_Q = 5;   // trips of the reduction over k = i, i + 8, ... in the first batch of loads: N = 40 in one
+constexpr int HEAD_S = 20;  // stages of the ordered sums per round trip
 template <bool PI = false>
 __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const int i, const int b, const bool valid,
                                         const int active_slot, bool& live, bool& retry, double& mu) {
@@ -385,15 +397,49 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
   double* st = W.st;
   int* si = W.si;
   const ltompc_options& o = K.o;
-  live = valid && !STI(SI_DONE);
+  // Everything the head can read on any of its paths, in ONE batch of loads ahead of the first decision: the instance's scalars
+  // (fetched where they were used, each was a memory round trip of its own, several of them behind a store: vmcnt counts loads
+  // and stores in order), the first HEAD_Q trips of the reduction over the stages k = i, i + 8, ... and the first HEAD_S stages
+  // of the ordered sums.  (Lanes with valid = false shadow a real instance: the loads are in bounds for them too.)
+  int done = STI(SI_DONE), retry_set = STI(SI_RETRY), passes = STI(SI_SWEEPS), reinit = STI(SI_REINIT), iters = STI(SI_ITERS);
+  int nacc = STI(SI_NACC), resto = STI(SI_RESTO), sincemu = STI(SI_SINCEMU), warm_set = STI(SI_WARM), fbarmed = STI(SI_FBARMED);
+  int nresto = STI(SI_NRESTO), nfallback = STI(SI_NFALLBACK);
+  double rho = STD(ST_RHO), c00 = STD(ST_C00), mu_now = STD(ST_MU), g0 = STD(ST_G0), eps_now = STD(ST_EPS);
+  double x0[8];  // (restart_from_primal, when the smoothing changes with it)
+#pragma unroll
+  for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
+  double r5[5][HEAD_Q], sm[HEAD_S], co[HEAD_S];
+#pragma unroll
+  for (int q = 0; q < HEAD_Q; q++) {
+    const int k = i + 8 * q < N ? i + 8 * q : N - 1;  // (past the horizon: a valid word, not used)
+    r5[0][q] = PL(W.RS, RS_rd, k, N), r5[1][q] = PL(W.RS, RS_rp, k, N), r5[2][q] = PL(W.RS, RS_cmax, k, N);
+    r5[3][q] = PL(W.RS, RS_cmin, k, N), r5[4][q] = PL(W.RS, RS_emax, k, N);
+  }
+#pragma unroll
+  for (int q = 0; q < HEAD_S; q++) {
+    const int k = q < N ? q : N - 1;
+    sm[q] = PL(W.RS, RS_smult, k, N), co[q] = PL(W.RS, RS_cost, k, N);
+  }
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (all of them in registers before the first use: left alone the compiler sinks the loads into the branches that use them)
+  asm volatile("" : "+v"(done), "+v"(retry_set), "+v"(passes), "+v"(reinit), "+v"(iters), "+v"(nacc), "+v"(resto), "+v"(sincemu), "+v"(warm_set),
+                    "+v"(fbarmed), "+v"(nresto), "+v"(nfallback), "+v"(rho), "+v"(c00), "+v"(mu_now), "+v"(g0), "+v"(eps_now));
+  asm volatile("" : "+v"(x0[0]), "+v"(x0[1]), "+v"(x0[2]), "+v"(x0[3]), "+v"(x0[4]), "+v"(x0[5]), "+v"(x0[6]), "+v"(x0[7]));
+#pragma unroll
+  for (int q = 0; q < HEAD_Q; q++) asm volatile("" : "+v"(r5[0][q]), "+v"(r5[1][q]), "+v"(r5[2][q]), "+v"(r5[3][q]), "+v"(r5[4][q]));
+#pragma unroll
+  for (int q = 0; q < HEAD_S; q += 4)
+    asm volatile("" : "+v"(sm[q]), "+v"(sm[q + 1]), "+v"(sm[q + 2]), "+v"(sm[q + 3]), "+v"(co[q]), "+v"(co[q + 1]), "+v"(co[q + 2]), "+v"(co[q + 3]));
+#endif
+  live = valid && !done;
   retry = false;
   mu = 0.0;
   if (!__any(live)) return false;
   // One sweep per launch: an instance whose sweep fails the inertia test repeats it in the NEXT launch with a larger
   // delta_w (its blocks stay in HBM, k_eval skips it) instead of looping here, so that a launch never takes longer
   // than one sweep however hard the worst instance of the batch is.
-  retry = live && STI(SI_RETRY);
-  const int passes = STI(SI_SWEEPS);  // passes used so far (see layout.h); the budget is options.max_iter of them
+  retry = live && retry_set;
+  // passes: used so far (see layout.h); the budget is options.max_iter of them
   if (live && passes > o.max_iter) {
     // (a head that one sweep per launch would never have run: the host loop issues max_iter + 1 of them; reached when sweeps were
     //  repeated inside launches and the pass before was the last one - e.g. the return from the restoration phase, which is
@@ -402,29 +448,39 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
     live = false, retry = false;
   }
   if (!__any(live)) return false;
-  const double rho = STD(ST_RHO);
   double rd = 0.0, rp = 0.0, cmax = 0.0, cmin = 1e300, emax = 0.0;
-  for (int k = i; k < N; k += 8) {
+#pragma unroll
+  for (int q = 0; q < HEAD_Q; q++)
+    if (i + 8 * q < N) {
+      rd = fmax(rd, r5[0][q]), rp = fmax(rp, r5[1][q]);
+      cmax = fmax(cmax, r5[2][q]), cmin = fmin(cmin, r5[3][q]);
+      emax = fmax(emax, r5[4][q]);
+    }
+  for (int k = i + 8 * HEAD_Q; k < N; k += 8) {  // (N > 8 HEAD_Q)
     rd = fmax(rd, PL(W.RS, RS_rd, k, N)), rp = fmax(rp, PL(W.RS, RS_rp, k, N));
     cmax = fmax(cmax, PL(W.RS, RS_cmax, k, N)), cmin = fmin(cmin, PL(W.RS, RS_cmin, k, N));
     emax = fmax(emax, PL(W.RS, RS_emax, k, N));
   }
   rd = grp_max(rd), rp = grp_max(rp), cmax = grp_max(cmax), cmin = grp_min(cmin), emax = grp_max(emax);
   double smult = 0.0, obj;
-  obj = STD(ST_C00);  // lterm(x_0), kept by k_init / d_pick
-  for (int k0 = 0; k0 < N; k0 += 8) {  // same order of additions as the serial kernel, eight loads in flight per round trip
-    double sm8[8], co8[8];
+  obj = c00;  // lterm(x_0), kept by k_init / d_pick
+  // same order of additions as the serial kernel, HEAD_S stages per round trip (the first of them came with the batch above)
 #pragma unroll
-    for (int q = 0; q < 8; q++) {
+  for (int q = 0; q < HEAD_S; q++)
+    if (q < N) smult += sm[q], obj += co[q];
+  for (int k0 = HEAD_S; k0 < N; k0 += HEAD_S) {
+    double sm8[HEAD_S], co8[HEAD_S];
+#pragma unroll
+    for (int q = 0; q < HEAD_S; q++) {
       const int k = k0 + q < N ? k0 + q : N - 1;
       sm8[q] = PL(W.RS, RS_smult, k, N), co8[q] = PL(W.RS, RS_cost, k, N);
     }
 #pragma unroll
-    for (int q = 0; q < 8; q++)
+    for (int q = 0; q < HEAD_S; q++)
       if (k0 + q < N) smult += sm8[q], obj += co8[q];
   }
   const int n_mult = N * (2 * NX + K.bd.ni) - (3 + K.bd.nel) + (rho > 0.0 ? 3 * (N - 1) : 0) + K.bd.nel * (N - 1);  // multipliers counted (the last slot has no nonlinear constraints; elastic pairs count twice)
-  mu = STD(ST_MU);
+  mu = mu_now;
   const double S = pen_scale(rho), iS = 1.0 / S;  // penalty scale (layout.h): 1 unless rho > RHO_UNIT
   double s_d = fmax(o.s_max, smult * iS / n_mult) / o.s_max;
   double E0 = fmax(fmax(rd * iS / s_d, rp), cmax * iS / s_d);
@@ -432,21 +488,20 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
   double Emu = fmax(fmax(rd * iS / s_d, rp), rcmu * iS / s_d);
   int term = -1;
   bool to_hard = false, escalate = false, fallback = false;
-  if (valid && i == 0 && STI(SI_REINIT)) STI(SI_REINIT) = 0, STI(SI_SHIFT) = 0;  // the evaluation before this head has re-initialised the slots
+  if (valid && i == 0 && reinit) STI(SI_REINIT) = 0, STI(SI_SHIFT) = 0;  // the evaluation before this head has re-initialised the slots
   if (live && !retry) {
-    int iters = STI(SI_ITERS);
     if (!isfinite(E0)) term = LTOMPC_STATUS_NUMERICAL;
     else if (E0 <= o.tol) term = LTOMPC_STATUS_SOLVED;
     else {
-      int na = (E0 <= o.acceptable_tol) ? STI(SI_NACC) + 1 : 0;
+      int na = (E0 <= o.acceptable_tol) ? nacc + 1 : 0;
       if (i == 0) STI(SI_NACC) = na;
       // (an escalated elastic problem only has to answer "is some elastic variable > 0 at the least violation": the acceptable
       //  level decides that at once - IPOPT's restoration phase does not iterate to the NLP's tolerance either; at S = 1e4 the
       //  unscaled dual residual sits at the rounding floor, 1e-4 on multipliers of 1e7, i.e. 1e-8 scaled)
-      if ((na >= o.acceptable_iter || (STI(SI_RESTO) == 1 && S > 1.0)) && E0 <= o.acceptable_tol) term = LTOMPC_STATUS_ACCEPTABLE;
+      if ((na >= o.acceptable_iter || (resto == 1 && S > 1.0)) && E0 <= o.acceptable_tol) term = LTOMPC_STATUS_ACCEPTABLE;
       if (term < 0 && (iters >= o.max_iter || passes >= o.max_iter)) term = LTOMPC_STATUS_MAX_ITER;
     }
-    if (STI(SI_RESTO) == 1 && (term == LTOMPC_STATUS_SOLVED || term == LTOMPC_STATUS_ACCEPTABLE)) {
+    if (resto == 1 && (term == LTOMPC_STATUS_SOLVED || term == LTOMPC_STATUS_ACCEPTABLE)) {
       // The elastic problem of the restoration phase has converged.  All elastic variables at (numerically) zero: its
       // solution is a KKT point of the hard-constrained NLP with the same multipliers (nu < rho): back to the hard
       // constraints, where the termination test is repeated on the hard problem's own KKT error (this launch does no
@@ -463,9 +518,9 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
       else term = LTOMPC_STATUS_INFEASIBLE;
     }
     int node0;
-    term = node0_rule(o, STD(ST_G0), term, node0);
+    term = node0_rule(o, g0, term, node0);
     if (i == 0) {
-      STD(ST_E0) = E0, STD(ST_OBJ) = obj, STD(ST_VIOL) = (node0 && term == LTOMPC_STATUS_INFEASIBLE) ? STD(ST_G0) : emax;
+      STD(ST_E0) = E0, STD(ST_OBJ) = obj, STD(ST_VIOL) = (node0 && term == LTOMPC_STATUS_INFEASIBLE) ? g0 : emax;
       if (node0) STI(SI_NODE0) = node0;
       if (term >= 0) STI(SI_STATUS) = term, STI(SI_DONE) = 1;
       if (to_hard) {
@@ -474,8 +529,8 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
         STI(SI_STEP) = 0, STI(SI_SKIP_EVAL) = 0;
       }
       if (escalate) {
-        restart_from_primal<PI>(K, W, b, fmin(rho * o.resto_rho_factor, o.resto_rho_max));
-        STI(SI_NRESTO) += 1;
+        restart_from_primal<PI>(K, W, b, fmin(rho * o.resto_rho_factor, o.resto_rho_max), eps_now, x0);
+        STI(SI_NRESTO) = nresto + 1;
       }
     }
     if (term >= 0) live = false;
@@ -504,14 +559,14 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
     // options.warm_fallback_iter: a solve that started at the small barrier parameter of a tuned warm start (mu_init_warm) and has
     // not decreased it for that many iterations is cycling around a point that is not central; once per solve it starts again
     // from its current primal point the way a solve after a failed one starts (multipliers 0, barrier at mu_init)
-    const int since = mu_changed ? 0 : STI(SI_SINCEMU) + 1;
-    const bool warm = STI(SI_WARM) != 0;
-    const bool recoverable = rho == 0.0 && STI(SI_RESTO) == 0 && o.resto_rho > 0.0;  // on the hard constraints, recovery steps still ahead
+    const int since = mu_changed ? 0 : sincemu + 1;
+    const bool warm = warm_set != 0;
+    const bool recoverable = rho == 0.0 && resto == 0 && o.resto_rho > 0.0;  // on the hard constraints, recovery steps still ahead
     // options.max_mu_stay (warm-started solves): this many iterations without a decrease of the barrier parameter - the iterates
     // wander or cycle (the filter holds FILTER_MAX pairs and forgets the oldest).  On the hard constraints the recovery steps
     // take over at the end of this iteration, elsewhere the solve ends STALLED.
     const bool stuck = warm && o.max_mu_stay > 0 && since >= o.max_mu_stay;
-    fallback = !(stuck && !recoverable) && STI(SI_FBARMED) && since >= o.warm_fallback_iter;
+    fallback = !(stuck && !recoverable) && fbarmed && since >= o.warm_fallback_iter;
     if (i == 0) {
       STI(SI_SINCEMU) = since;
       if (stuck && !recoverable) STI(SI_STATUS) = LTOMPC_STATUS_STALLED, STI(SI_DONE) = 1;
@@ -526,8 +581,8 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
       }
       STD(ST_TAU) = fmax(o.tau_min, 1.0 - mu * iS);
       if (fallback) {
-        STI(SI_FBARMED) = 0, STI(SI_NFALLBACK) += 1;
-        restart_from_primal<PI>(K, W, b, rho);
+        STI(SI_FBARMED) = 0, STI(SI_NFALLBACK) = nfallback + 1;
+        restart_from_primal<PI>(K, W, b, rho, eps_now, x0);
       }
     }
     if (fallback || (stuck && !recoverable)) live = false;
