@@ -399,6 +399,49 @@ int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, doub
 int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_p_dev, double* grad_theta_dev,
                        int* ok_dev);
 
+/* Adjoint gradients w.r.t. the track tables: the gradient of a scalar loss L(X, U) of the predicted trajectory of
+ * the last solve w.r.t. the knot values y[r][j] of the LTOMPC_TABLE_VALUE_ROWS = 4 value rows r = kappa, n_left, n_right, v_ref
+ * (the rows of ltompc_set_table_values; the grids s_kappa and s_arc are not differentiated), from the cotangents gX, gU of
+ * ltompc_get_adjoint, summed over the instances of the handle (they share the tables):
+ *     grad_tables[r][j] = sum_b ( sum_{k,i} gX_b[k,i] dX_b[k,i]/dy[r][j] + sum_{k,c} gU_b[k,c] dU_b[k,c]/dy[r][j] )
+ * Definition: that of ltompc_get_sensitivities - the barrier problem at the final iterate with the final barrier parameter and
+ * table smoothing, the KKT matrix with delta_w = 0, the same instances.  ok[b] equals ltompc_get_sensitivities' ok[b] bit for bit;
+ * an instance with ok[b] = 0 contributes exactly 0.  Block 0 of gX does not enter (x0 is data).  Knots that no look-up of any
+ * predicted trajectory touches get exactly 0.
+ *
+ * The tables enter interval k of instance b through ten scalars, the value and the slope that the look-ups returned:
+ *     slot_grad[b][k][0..9] = dL/d( kappa(s(c_k)), kappa'(s(c_k)), kappa(s(x_{k+1})), kappa'(s(x_{k+1})),
+ *                                   n_left, n_left', n_right, n_right', v_ref, v_ref' at s(x_{k+1}) )
+ * (c_k: the first Radau point of interval k; the last six are 0 for k = N - 1: node N has no track row and no v_ref term).
+ * slot_grad is deterministic: the same solve and cotangent give the same bits, whatever the batch, the packing or the split
+ * over handles.  It is what a caller with a table parametrisation of its own (a spline race line) chains through.  grad_tables
+ * is slot_grad scattered to the knots with the weights of the piece-wise linear basis (with the rounding of the knots that the
+ * solve used: at most four knots per look-up) and summed over the instances with fp64 atomic adds: its last bits depend on
+ * the order in which the adds arrive and can differ between two calls.  With periodic_tables the first and the last knot of a
+ * row are reported separately.
+ *
+ * Inputs, in the caller's instance order:  gX  batch x (N+1) x 8;  gU  batch x N x 2.  Either may be NULL (= zeros); both NULL is a
+ * usage error.  Outputs, any may be NULL:  grad_tables  4 x n_table (overwritten, not accumulated);  slot_grad  batch x N x 10 in the
+ * caller's instance order;  ok  batch ints.
+ * ltompc_get_adjoint_tables: host pointers.  A non-finite cotangent is a usage error that names the instance.
+ * ltompc_adjoint_tables_dev: device pointers, enqueues only, on the handle's stream.  The cotangents are NOT checked.  The first
+ *   request on a handle allocates the pass's buffers and synchronises once (as for ltompc_sensitivities_dev).
+ *
+ * The result refers to the last solve of each instance; before any solve, after set_initial_guess(_dev) and after
+ * ltompc_set_table_values(_dev) a call is a usage error.  A handle with ell_penalty > 0 or ptv != 0 is a usage error, as for
+ * ltompc_get_param_sensitivities; unlike grad_theta the pass needs no u_prev, so a call after rollout_dev works.  With
+ * per-instance rows the gradients are those at the rows the solve used.  The re-linearisation and the factorisation are shared
+ * with the other passes (whichever runs first for a solve makes them); nothing is kept per cotangent.  The pass writes buffers of
+ * its own only: every later make_step, rollout or other pass gives the bits it would have given without it. */
+int ltompc_get_adjoint_tables(ltompc_handle h, const double* gX, const double* gU, double* grad_tables, double* slot_grad, int* ok);
+int ltompc_adjoint_tables_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_tables_dev, double* slot_grad_dev,
+                              int* ok_dev);
+/* ltompc_adjoint_tables_dev, except that grad_tables_dev is ADDED TO instead of overwritten (slot_grad_dev and ok_dev are written
+ * as there): the handles of a batch that is split over several handles with the same tables call the plain form on the first
+ * part and this one on the others, one after the other, and get the sum over the whole batch in one 4 x n_table array. */
+int ltompc_adjoint_tables_add_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_tables_dev,
+                                  double* slot_grad_dev, int* ok_dev);
+
 /* ltompc_get_prediction into device memory: X_dev (row-major batch x (N+1) x 8) and U_dev (batch x N x 2) in the caller's
  * instance order, either may be NULL.  Enqueues only, on the handle's stream.  Unlike ltompc_get_prediction it reads the
  * instances where they are and does not restore the caller's order inside the handle: a device-side loop (a loss on the
@@ -447,6 +490,28 @@ int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_d
  * referring to the u_prev that solve used. */
 int ltompc_set_u_prev(ltompc_handle h, const double* u_prev);
 int ltompc_set_u_prev_dev(ltompc_handle h, const double* u_prev_dev);
+
+/* Settable table values: overwrite one of the LTOMPC_TABLE_VALUE_ROWS = 4 value rows of the handle's look-up tables, so that a
+ * caller who tunes the race line or the reference-speed profile keeps the handle and the warm start of its instances.
+ *   row     0 kappa, 1 n_left, 2 n_right, 3 v_ref;   values  n_table doubles (the n_table of ltompc_create).
+ * The grids s_kappa and s_arc, n_table and what ltompc_create derived from the grids (the interval estimate of the look-ups,
+ * the period of options.periodic_tables) stay; they cannot be set.  With periodic_tables the caller keeps
+ * values[n_table - 1] == values[0] (the kink at the seam is not rounded, as at ltompc_create); this is not checked.
+ * ltompc_set_table_values: host pointer.  Every entry is checked finite; a bad entry is a usage error that names the knot and
+ *   leaves the handle unchanged.  Returns when the row is in place.
+ * ltompc_set_table_values_dev: a device pointer, enqueues only, on the handle's stream.  NOT checked.
+ * ltompc_get_table_values: the row in effect (host, out), after everything enqueued on the handle's stream before it.
+ * A set takes effect for everything enqueued after it: the next make_step, make_step_dev and rollout_dev solve with the new
+ * row (bit for bit what a handle created with it gives from the same starting point), and ltompc_plant_step(_dev),
+ * ltompc_plant_sensitivities(_dev) and the rollout's plant steps read the new kappa.  It does not touch the warm start (the
+ * iterate, the multipliers, u_prev, the per-instance rows).  It discards the derivative state of the last solve - the cached
+ * factorisation belongs to the old tables: until the next solve every derivative request (ltompc_get_sensitivities,
+ * ltompc_get_param_sensitivities, ltompc_get_adjoint, ltompc_get_jvp, ltompc_loop_tick and their _dev forms) is the usage
+ * error of a handle that has not solved yet. */
+#define LTOMPC_TABLE_VALUE_ROWS 4
+int ltompc_set_table_values(ltompc_handle h, int row, const double* values);
+int ltompc_set_table_values_dev(ltompc_handle h, int row, const double* values_dev);
+int ltompc_get_table_values(ltompc_handle h, int row, double* values);
 
 /* Per-instance vehicle and cost parameters.  Instance b may have its own row theta_b: the LTOMPC_NTHETA = 16
  * values of ltompc_get_param_sensitivities' columns, in that order and in natural units.  Every other field of ltompc_params

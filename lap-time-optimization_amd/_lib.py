@@ -16,6 +16,10 @@ NTHETA = len(THETA_NAMES)
 # columns of ltompc_get_loop_sensitivities (LTOMPC_NLOOP): the initial state, then theta
 LOOP_NAMES = tuple(f"x_init[{i}]" for i in range(8)) + THETA_NAMES
 NLOOP = len(LOOP_NAMES)
+# rows of ltompc_set_table_values and of grad_tables (LTOMPC_TABLE_VALUE_ROWS): the value rows of the look-up tables, in this order
+TABLE_ROW_NAMES = ("kappa", "n_left", "n_right", "v_ref")
+# the ten scalars of slot_grad (ltompc_get_adjoint_tables): value and slope (') of kappa at c_k and at x_{k+1}, of the others at x_{k+1}
+TABLE_SLOT_NAMES = ("kappa_c", "kappa_c'", "kappa_x", "kappa_x'", "n_left", "n_left'", "n_right", "n_right'", "v_ref", "v_ref'")
 NO_BOUND = 1.0e30
 STATUS_NAMES = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "numerical", 4: "stalled", 5: "infeasible"}
 
@@ -73,11 +77,17 @@ def lib() -> C.CDLL:
         L.ltompc_param_sensitivities_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_get_adjoint.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
         L.ltompc_adjoint_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_get_adjoint_tables.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
+        L.ltompc_adjoint_tables_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_adjoint_tables_add_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_get_prediction_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_get_jvp.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
         L.ltompc_jvp_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_set_u_prev.argtypes = [C.c_void_p, _dp]
         L.ltompc_set_u_prev_dev.argtypes = [C.c_void_p, C.c_void_p]
+        L.ltompc_set_table_values.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.ltompc_set_table_values_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.ltompc_get_table_values.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ltompc_set_instance_params.argtypes = [C.c_void_p, _dp]
         L.ltompc_set_instance_params_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_get_instance_params.argtypes = [C.c_void_p, _dp]

@@ -1,6 +1,7 @@
 """torch.autograd layer over a BatchedMPC handle: the solve and the plant step as differentiable functions of device tensors.
 
-    u0, X, U, ok = mpc_solve(mpc, x0, u_prev, theta)      # make_step_dev + prediction_dev; backward: adjoint_dev, forward mode: jvp_dev
+    u0, X, U, ok = mpc_solve(mpc, x0, u_prev, theta, tables)   # make_step_dev + prediction_dev; backward: adjoint_dev (and
+                                                               # adjoint_tables_dev for tables), forward mode: jvp_dev
     x_next       = plant_step(mpc, x, u0, theta, n_sub)   # plant_sensitivities_dev; backward: its Jacobians through torch.einsum
 
 so that one tick `u0 = solve(x, u_prev, th); x = plant(x, u0, th)` is differentiable end to end and a T-tick loop backpropagates
@@ -19,7 +20,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-NX, NU, NTHETA = 8, 2, 16
+NX, NU, NTHETA, NROWS = 8, 2, 16, 4
 
 
 def _check(mpc, name, t, shape):
@@ -53,15 +54,20 @@ def _fresh(mpc, count, what):
 
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mpc, x0, u_prev, theta):
+    def forward(ctx, mpc, x0, u_prev, theta, tables):
         B, N = mpc.B, mpc.N
         _check(mpc, "mpc_solve: x0", x0, (B, NX))
+        if tables is not None:
+            _check(mpc, "mpc_solve: tables", tables, (NROWS, mpc.n_table))  # (the handle copies n_table doubles per row)
         if u_prev is not None:
             _check(mpc, "mpc_solve: u_prev", u_prev, (B, NU))
         if theta is not None:
             _check(mpc, "mpc_solve: theta", theta, (B, NTHETA))
         u0, X, U, ok = _new(mpc, B, NU), _new(mpc, B, N + 1, NX), _new(mpc, B, N, NU), _new(mpc, B, dtype=torch.int32)
         _sync_torch(mpc)
+        if tables is not None:
+            for r in range(NROWS):
+                mpc.set_table_values_dev(r, tables[r].data_ptr())
         if theta is not None:
             mpc.set_theta_dev(theta.data_ptr())
         if u_prev is not None:
@@ -70,7 +76,7 @@ class _Solve(torch.autograd.Function):
         mpc.prediction_dev(X.data_ptr(), U.data_ptr())
         mpc.sensitivities_dev(0, ok.data_ptr())  # (ok, and the factorisation that backward / jvp share)
         mpc.synchronize()
-        ctx.mpc, ctx.count, ctx.has = mpc, mpc.solve_count, (u_prev is not None, theta is not None)
+        ctx.mpc, ctx.count, ctx.has = mpc, mpc.solve_count, (u_prev is not None, theta is not None, tables is not None)
         ctx.mark_non_differentiable(ok)
         return u0, X, U, ok
 
@@ -87,14 +93,21 @@ class _Solve(torch.autograd.Function):
         want_theta = ctx.has[1] and ctx.needs_input_grad[3]
         gp = _new(mpc, B, NX + NU)
         gth = _new(mpc, B, NTHETA) if want_theta else None
+        want_tables = ctx.has[2] and ctx.needs_input_grad[4]
+        gtab = _new(mpc, NROWS, mpc.n_table) if want_tables else None
         _sync_torch(mpc)
         mpc.adjoint_dev(gX.data_ptr(), gU.data_ptr(), gp.data_ptr(), gth.data_ptr() if want_theta else 0, 0)
+        if want_tables:
+            mpc.adjoint_tables_dev(gX.data_ptr(), gU.data_ptr(), gtab.data_ptr(), 0, 0)
         mpc.synchronize()
-        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth
+        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth, gtab
 
     @staticmethod
-    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta):
+    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta, t_tables):
         mpc = ctx.mpc
+        if t_tables is not None and ctx.has[2] and bool((t_tables != 0).any()):  # (torch hands zeros for an input without a tangent)
+            raise RuntimeError("mpc_solve jvp: forward mode is not available for `tables` (there is no directional pass in the "
+                               "tables; use reverse mode, which returns grad_tables)")
         _fresh(mpc, ctx.count, "jvp")
         B, N = mpc.B, mpc.N
         if not ctx.has[0]:
@@ -163,21 +176,31 @@ class _Plant(torch.autograd.Function):
         return out
 
 
-def mpc_solve(mpc, x0, u_prev=None, theta=None):
+def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None):
     """One solve of the handle as a differentiable function: (u0 (B,2), X (B,N+1,8), U (B,N,2), ok (B,) int32) of x0 (B,8),
-    u_prev (B,2; None: the one the handle makes itself, no gradient) and theta (B,16 per-instance rows in THETA_NAMES order;
-    None: the rows or params in effect, no gradient).
+    u_prev (B,2; None: the one the handle makes itself, no gradient), theta (B,16 per-instance rows in THETA_NAMES order;
+    None: the rows or params in effect, no gradient) and tables ((4, n_table): the value rows kappa, n_left, n_right, v_ref
+    of the handle's look-up tables, TABLE_ROW_NAMES order; None: the rows in effect, no gradient).
 
-    Forward: set_theta_dev / set_u_prev_dev for the arguments given, make_step_dev, prediction_dev (and ok of the sensitivity
-    pass).  Backward: adjoint_dev with the cotangent of u0 added to gU[:, 0]; grad_theta is requested only when theta needs a
-    gradient.  Forward mode (torch.autograd.forward_ad): jvp_dev.  ok is not differentiable; where it is 0 all derivatives are 0.
-    Torch's current stream is synchronised before the calls and the handle after them."""
-    return _Solve.apply(mpc, x0, u_prev, theta)
+    Forward: set_table_values_dev (the four rows) / set_theta_dev / set_u_prev_dev for the arguments given, make_step_dev,
+    prediction_dev (and ok of the sensitivity pass).  Backward: adjoint_dev with the cotangent of u0 added to gU[:, 0];
+    grad_theta is requested only when theta needs a gradient, and adjoint_tables_dev only when tables does (its result is the
+    sum over the instances, which share the tables).  Forward mode (torch.autograd.forward_ad): jvp_dev; a tangent in `tables`
+    raises a RuntimeError (there is no directional pass in the tables).  ok is not differentiable; where it is 0 all
+    derivatives are 0.  Torch's current stream is synchronised before the calls and the handle after them.
+
+    The tables set here stay on the handle: they are the CONTROLLER's belief of the track from then on, and the handle's plant
+    step reads the kappa row too (plant_step below takes no tables and has no gradient w.r.t. them)."""
+    return _Solve.apply(mpc, x0, u_prev, theta, tables)
 
 
 def plant_step(mpc, x, u, theta=None, n_sub=400):
     """The plant step as a differentiable function: x_next (B,8; the bits of plant_step_dev) of x (B,8), u (B,2) and theta
     (B,16 rows, set on the handle as set_theta_dev does; None: the rows or params in effect, no gradient).  Forward:
     plant_sensitivities_dev (dxn_dtheta only when theta needs a gradient); backward contracts the stored Jacobians with
-    torch.einsum.  Same stream rule as mpc_solve."""
+    torch.einsum.  Same stream rule as mpc_solve.
+
+    There is no tables input: the tables that mpc_solve differentiates are the controller's belief, the plant's track is the
+    physical one.  A closed loop of mpc_solve and plant_step therefore backpropagates to n_left, n_right, v_ref and the
+    controller's kappa through the solves only; the plant's own dependence on kappa is not differentiated."""
     return _Plant.apply(mpc, x, u, theta, n_sub)

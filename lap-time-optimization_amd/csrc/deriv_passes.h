@@ -1,5 +1,6 @@
-// deriv_passes.h — host drivers and C entry points of the derivative passes on the final iterate of a solve (DESIGN.md §9-§12):
-// sensitivities w.r.t. (x0, u_prev) and theta, the adjoint of a trajectory loss, their product with one direction, the plant-step sensitivities and the closed loop.
+// deriv_passes.h — host drivers and C entry points of the derivative passes on the final iterate of a solve (DESIGN.md §9-§14):
+// sensitivities w.r.t. (x0, u_prev) and theta, the adjoint of a trajectory loss (w.r.t. those and w.r.t. the track tables), their
+// product with one direction, the plant-step sensitivities and the closed loop.
 // Part of ltompc.hip's translation unit, after ltompc_solver and its helpers; the passes' state is ltompc_solver::dv (DerivState).
 #pragma once
 
@@ -41,7 +42,7 @@ void sens_factorise(ltompc_solver* h) {
 // trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
 int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
   DerivState& D = h->dv;
-  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess discards the last solve)");
+  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess and set_table_values discard the last solve)");
   const int B = h->B, N = h->N, Bp = h->Bp;
   if (!D.d_Ws) {
     Work& Ws = D.Ws = h->W;
@@ -146,6 +147,42 @@ int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, co
   else
     hipLaunchKernelGGL(k_adj_sweep, dim3(Bp / 8), dim3(64), 0, h->stream, D.Ws, h->K.p.r_du[0], h->K.p.r_du[1], (const double*)D.d_psens_uprev,
                        (const double*)D.d_psens_pv, (const int*)D.d_sens_ok, gX_dev, gU_dev, D.d_adj_aj, D.d_adj_gp, gth);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The table-gradient pass of the last solve (table_sensitivity.h) for one cotangent (device pointers, caller's order; either may
+// be null), into d_tab_sg and d_tab_gt: the factorisation when not there, the sweep that keeps the adjoint trajectory, the
+// per-slot contraction, then the scatter to the knots into the zeroed d_tab_gt.  It needs no u_prev, so it also runs after a
+// rollout.  Once its buffers exist it only enqueues.
+int tab_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, const char* who) {
+  DerivState& D = h->dv;
+  if (!gX_dev && !gU_dev) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  if (sens_compute(h, false, who)) return -1;  // (ok; the usage error before a solve comes from here)
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (!D.d_tab_tj) {
+    if (h->dalloc(&D.d_tab_tj, (size_t)TJ_NF * N * Bp, true) || h->dalloc(&D.d_tab_sg, (size_t)TS_NS * N * B) ||
+        h->dalloc(&D.d_tab_gt, (size_t)TAB_ROWS * h->n_table))
+      return -1;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  }
+  sens_factorise(h);
+  const dim3 slots((N * Bp + 63) / 64), block(64);
+  if (h->pi_solve) {
+    hipLaunchKernelGGL(k_adj_sweep_tab_pi, dim3(Bp / 8), block, 0, h->stream, D.Wspi, gX_dev, gU_dev, D.d_tab_tj);
+    hipLaunchKernelGGL(h->ref_eval ? k_tab_cond_pi<BoundsRef> : k_tab_cond_pi<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
+                       (const WorkPI*)h->d_Wpi, (const double*)D.d_tab_tj, (const int*)D.d_sens_ok, D.d_tab_sg);
+  } else {
+    hipLaunchKernelGGL(k_adj_sweep_tab, dim3(Bp / 8), block, 0, h->stream, D.Ws, h->K.p.r_du[0], h->K.p.r_du[1], gX_dev, gU_dev, D.d_tab_tj);
+    hipLaunchKernelGGL(h->ref_eval ? k_tab_cond<BoundsRef> : k_tab_cond<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
+                       (const Work*)h->d_W, (const double*)D.d_tab_tj, (const int*)D.d_sens_ok, D.d_tab_sg);
+  }
+  HIPCHECK(hipMemsetAsync(D.d_tab_gt, 0, sizeof(double) * TAB_ROWS * h->n_table, h->stream));
+  const size_t nthreads = (size_t)3 * N * Bp;
+  hipLaunchKernelGGL(k_tab_scatter, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, h->stream, (const Consts*)h->d_K, h->W,
+                     (const int*)D.d_sens_ok, (const double*)D.d_tab_sg, D.d_tab_gt);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -289,6 +326,55 @@ int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, doub
   if (gU) HIPCHECK(hipMemcpyAsync(D.d_adj_gU, gU, sizeof(double) * N * 2 * B, hipMemcpyHostToDevice, h->stream));
   if (adj_compute(h, gX ? D.d_adj_gX : nullptr, gU ? D.d_adj_gU : nullptr, grad_theta != nullptr, who)) return -1;
   if (copy_out(h, D2H, grad_p, D.d_adj_gp, ADJ_NP * B) || copy_out(h, D2H, grad_theta, D.d_adj_gth, PS_NT * B) ||
+      copy_out(h, D2H, ok, D.d_sens_ok, B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_adjoint_tables_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_tables_dev, double* slot_grad_dev,
+                              int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_tables_dev")) return -1;
+  if (copy_out(h, D2D, grad_tables_dev, h->dv.d_tab_gt, (size_t)TAB_ROWS * h->n_table)) return -1;
+  if (copy_out(h, D2D, slot_grad_dev, h->dv.d_tab_sg, (size_t)TS_NS * h->N * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_adjoint_tables_add_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_tables_dev, double* slot_grad_dev,
+                                  int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_tables_add_dev")) return -1;
+  if (grad_tables_dev) {
+    const int n = TAB_ROWS * h->n_table;
+    hipLaunchKernelGGL(k_tab_add, dim3((n + 255) / 256), dim3(256), 0, h->stream, grad_tables_dev, (const double*)h->dv.d_tab_gt, n);
+    HIPCHECK(hipGetLastError());
+  }
+  if (copy_out(h, D2D, slot_grad_dev, h->dv.d_tab_sg, (size_t)TS_NS * h->N * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_adjoint_tables(ltompc_handle h, const double* gX, const double* gU, double* grad_tables, double* slot_grad, int* ok) {
+  const char* who = "ltompc_get_adjoint_tables";
+  if (!h) return fail("null handle");
+  if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  const size_t B = h->B, N = h->N;
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; gX && e < (N + 1) * 8; e++) fin = fin && std::isfinite(gX[b * (N + 1) * 8 + e]);
+    for (size_t e = 0; gU && e < N * 2; e++) fin = fin && std::isfinite(gU[b * N * 2 + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite cotangent of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  DerivState& D = h->dv;
+  if (gX && !D.d_adj_gX && h->dalloc(&D.d_adj_gX, (N + 1) * 8 * B)) return -1;
+  if (gU && !D.d_adj_gU && h->dalloc(&D.d_adj_gU, N * 2 * B)) return -1;
+  if (gX) HIPCHECK(hipMemcpyAsync(D.d_adj_gX, gX, sizeof(double) * (N + 1) * 8 * B, hipMemcpyHostToDevice, h->stream));
+  if (gU) HIPCHECK(hipMemcpyAsync(D.d_adj_gU, gU, sizeof(double) * N * 2 * B, hipMemcpyHostToDevice, h->stream));
+  if (tab_compute(h, gX ? D.d_adj_gX : nullptr, gU ? D.d_adj_gU : nullptr, who)) return -1;
+  if (copy_out(h, D2H, grad_tables, D.d_tab_gt, (size_t)TAB_ROWS * h->n_table) || copy_out(h, D2H, slot_grad, D.d_tab_sg, TS_NS * N * B) ||
       copy_out(h, D2H, ok, D.d_sens_ok, B))
     return -1;
   HIPCHECK(hipStreamSynchronize(h->stream));

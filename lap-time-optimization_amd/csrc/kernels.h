@@ -32,7 +32,10 @@
 //   plant_sensitivity.h k_plant_sens: the derivative of k_plant's discrete RK4 map w.r.t. (x, u, theta) (ltompc_plant_sensitivities);
 //                 k_loop_accum: the closed-loop recursion that chains it with the du0 outputs of the two forward passes over many
 //                 ticks (ltompc_loop_*)
-//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the five headers above
+//   table_sensitivity.h k_adj_sweep_tab, k_tab_cond, k_tab_scatter: the gradient of a loss of the predicted trajectory w.r.t. the knot
+//                 values of the track tables (ltompc_get_adjoint_tables): adjoint.h's recursion keeping its trajectory,
+//                 the per-slot contraction with the condensed columns of the ten look-up results, the scatter to the knots (lut_basis)
+//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the six headers above
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
@@ -50,3 +53,4 @@
 #include "adjoint.h"
 #include "jvp.h"
 #include "plant_sensitivity.h"
+#include "table_sensitivity.h"

@@ -46,7 +46,7 @@ struct DerivState {
   bool loop_fresh = false;  // a make_step has run since the last tick of the closed loop
   int loop_mode = 0;        // of the closed loop begun last (0: none)
 
-  // a solve starts or an initial guess overwrites the iterate: nothing to differentiate, nothing computed, nothing stored
+  // a solve starts, an initial guess overwrites the iterate or a table row is set: nothing to differentiate, nothing computed, nothing stored
   void discard() { sens = Sens::no_solve, psens = Psens::none, fact = pv_valid = kept_uprev = false; }
   // a solve has finished; kept_u: it was a make_step, which keeps each instance's u_prev
   void solved(const bool kept_u) { sens = Sens::solved, kept_uprev = kept_u, loop_fresh = loop_fresh || kept_u; }
@@ -69,6 +69,8 @@ struct DerivState {
   // directional pass (jvp.h): the kff planes, and the staging of the host form's directions and results
   double *d_jvp_jv = nullptr, *d_jvp_dp = nullptr, *d_jvp_dth = nullptr, *d_jvp_tX = nullptr, *d_jvp_tU = nullptr;
   int *d_loop_ok = nullptr, *d_loop_ticks = nullptr;
+  // table-gradient pass (table_sensitivity.h): the adjoint trajectory planes, slot_grad (B x N x 10) and grad_tables (4 x n_table)
+  double *d_tab_tj = nullptr, *d_tab_sg = nullptr, *d_tab_gt = nullptr;
 };
 
 struct ltompc_solver {
@@ -725,6 +727,54 @@ int ltompc_set_u_prev(ltompc_handle h, const double* u_prev) {
   HIPCHECK(hipSetDevice(h->device));
   HIPCHECK(hipMemcpyAsync(h->d_u0_rm, u_prev, sizeof(double) * 2 * h->B, hipMemcpyHostToDevice, h->stream));
   if (ltompc_set_u_prev_dev(h, h->d_u0_rm)) return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Value row r of ltompc_set_table_values (kappa, n_left, n_right, v_ref) inside d_tables (LTOMPC_TABLE_ROWS x n_table)
+double* table_value_row(ltompc_solver* h, const int row) {
+  static const int at[LTOMPC_TABLE_VALUE_ROWS] = {1, 3, 4, 5};
+  return h->d_tables + (size_t)at[row] * h->n_table;
+}
+
+int table_row_check(ltompc_solver* h, const int row, const void* values, const char* who) {
+  if (!h || !values) return fail(std::string(who) + ": null argument");
+  if (row < 0 || row >= LTOMPC_TABLE_VALUE_ROWS) return fail(std::string(who) + ": row must be 0 (kappa), 1 (n_left), 2 (n_right) or 3 (v_ref)");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ltompc_set_table_values_dev(ltompc_handle h, int row, const double* values_dev) {
+  if (table_row_check(h, row, values_dev, "ltompc_set_table_values_dev")) return -1;
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipMemcpyAsync(table_value_row(h, row), values_dev, sizeof(double) * h->n_table, hipMemcpyDeviceToDevice, h->stream));
+  h->dv.discard();  // (the cached factorisation and everything computed from it belong to the old tables)
+  return 0;
+}
+
+int ltompc_set_table_values(ltompc_handle h, int row, const double* values) {
+  const char* who = "ltompc_set_table_values";
+  if (table_row_check(h, row, values, who)) return -1;
+  for (int i = 0; i < h->n_table; i++)
+    if (!std::isfinite(values[i])) return fail(std::string(who) + ": non-finite value at knot " + std::to_string(i));
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipMemcpyAsync(table_value_row(h, row), values, sizeof(double) * h->n_table, hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->dv.discard();
+  return 0;
+}
+
+int ltompc_get_table_values(ltompc_handle h, int row, double* values) {
+  if (table_row_check(h, row, values, "ltompc_get_table_values")) return -1;
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipMemcpyAsync(values, table_value_row(h, row), sizeof(double) * h->n_table, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
 }

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LOOP_NAMES, NLOOP, NTHETA, NX, NU, THETA_NAMES, Options, Params, check, dptr, iptr, lib
+from ._lib import LOOP_NAMES, NLOOP, NTHETA, NX, NU, TABLE_ROW_NAMES, TABLE_SLOT_NAMES, THETA_NAMES, Options, Params, check, dptr, iptr, lib
 from .tables import TrackTables
 
 KERNEL_CLASSES = ("eval", "riccati", "expand", "linesearch", "pick", "update", "riccati1", "step1")  # include/ltompc.h
@@ -25,6 +25,7 @@ class BatchedMPC:
         self.params = params or _lib.default_params()
         self.options = options or _lib.default_options()
         self._tab = tables.packed()
+        self.n_table = int(self._tab.shape[1])  # knots per table row (autograd.py checks `tables` against it)
         self._h = C.c_void_p()
         check(lib().ltompc_create(C.byref(self.params), C.byref(self.options), dptr(self._tab), self._tab.shape[1],
                                   self.N, self.B, int(device), C.byref(self._h)))
@@ -205,6 +206,43 @@ class BatchedMPC:
         check(lib().ltompc_adjoint_dev(self._h, C.c_void_p(gX_ptr or None), C.c_void_p(gU_ptr or None), C.c_void_p(grad_p_ptr or None),
                                        C.c_void_p(grad_theta_ptr or None), C.c_void_p(ok_ptr or None)))
 
+    # ---- adjoint gradients w.r.t. the track tables (ltompc_get_adjoint_tables) -----------------------------------
+    def adjoint_tables(self, gX=None, gU=None, slots: bool = False):
+        """Gradient of a scalar loss L(X, U) of the last solve's predicted trajectory w.r.t. the knot values of the four value
+        rows TABLE_ROW_NAMES (kappa, n_left, n_right, v_ref), from its cotangents gX = dL/dX (B,N+1,8) and gU = dL/dU (B,N,2)
+        (None: zeros; not both), summed over the instances of the handle.
+
+        Returns grad_tables (4, n_table), names, ok (B,) bool (the same as sensitivities()' ok; an instance where it is False
+        contributes 0) and, with slots=True, slot_grad (B,N,10): the gradient w.r.t. the ten look-up results of every interval
+        (slot_names = TABLE_SLOT_NAMES), which is deterministic and what a table parametrisation of the caller's own chains
+        through.  The last bits of grad_tables can differ between two calls (atomic adds over the instances)."""
+        B, N = self.B, self.N
+        if gX is not None:
+            gX = np.ascontiguousarray(gX, dtype=np.float64)
+            if gX.shape != (B, N + 1, NX):
+                raise ValueError(f"adjoint_tables: gX must have shape {(B, N + 1, NX)}, got {gX.shape}")
+        if gU is not None:
+            gU = np.ascontiguousarray(gU, dtype=np.float64)
+            if gU.shape != (B, N, NU):
+                raise ValueError(f"adjoint_tables: gU must have shape {(B, N, NU)}, got {gU.shape}")
+        gt, ok = np.empty((len(TABLE_ROW_NAMES), self._tab.shape[1])), np.empty(B, dtype=np.int32)
+        sg = np.empty((B, N, len(TABLE_SLOT_NAMES))) if slots else None
+        check(lib().ltompc_get_adjoint_tables(self._h, dptr(gX) if gX is not None else None, dptr(gU) if gU is not None else None,
+                                              dptr(gt), dptr(sg) if slots else None, iptr(ok)))
+        out = dict(grad_tables=gt, names=TABLE_ROW_NAMES, ok=ok != 0)
+        if slots:
+            out.update(slot_grad=sg, slot_names=TABLE_SLOT_NAMES)
+        return out
+
+    def adjoint_tables_dev(self, gX_ptr: int, gU_ptr: int, grad_tables_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0, add: bool = False):
+        """Enqueue the table-gradient pass of the last solve on the handle's stream: cotangents from device arrays (B,N+1,8) /
+        (B,N,2) of doubles (0: zeros; not both, NOT checked for finiteness), results into device arrays (4,n_table) / (B,N,10)
+        doubles / (B,) int32 (0: not wanted).  add=True: grad_tables is added to the array instead of overwriting it
+        (ltompc_adjoint_tables_add_dev: the parts of a split batch)."""
+        fn = lib().ltompc_adjoint_tables_add_dev if add else lib().ltompc_adjoint_tables_dev
+        check(fn(self._h, C.c_void_p(gX_ptr or None), C.c_void_p(gU_ptr or None), C.c_void_p(grad_tables_ptr or None),
+                 C.c_void_p(slot_grad_ptr or None), C.c_void_p(ok_ptr or None)))
+
     # ---- directional sensitivities: the Jacobians times one direction (ltompc_get_jvp, DESIGN.md §13) ----------------------
     def jvp(self, dp=None, dtheta=None):
         """Directional derivative of the last solve's predicted trajectory along dp (B,10: x0[0..7], u_prev[0..1]) and dtheta
@@ -297,6 +335,35 @@ class BatchedMPC:
         """The handle's values of the 16 parameters of param_sensitivities(), in THETA_NAMES order."""
         p = self.params
         return np.array([getattr(p, n) for n in THETA_NAMES[:-2]] + [p.r_du[0], p.r_du[1]])
+
+    # ---- settable table values (ltompc_set_table_values) ----------------------------------------------------------------
+    def set_table_values(self, row, values):
+        """Overwrite one value row of the handle's look-up tables: row = "kappa", "n_left", "n_right" or "v_ref" (or its index
+        in TABLE_ROW_NAMES), values (n_table,) finite.  The grids stay.  From the next solve, plant step and rollout on; the
+        warm start is kept; the last solve's derivatives are discarded (a derivative request before the next solve raises, and
+        solved_parameters() is None).  `self.tables` stays the creation-time TrackTables; table_values() reads the rows in effect."""
+        r = _table_row(row)
+        v = _table_values(values, self._tab.shape[1])
+        check(lib().ltompc_set_table_values(self._h, r, dptr(v)))
+        self._tables_changed()
+
+    def set_table_values_dev(self, row, values_ptr: int):
+        """set_table_values from a device array of (n_table,) float64 (ltompc_set_table_values_dev): enqueued on the handle's
+        stream, NOT checked."""
+        check(lib().ltompc_set_table_values_dev(self._h, _table_row(row), C.c_void_p(values_ptr)))
+        self._tables_changed()
+
+    def _tables_changed(self):
+        self._solved = None
+        self._fb = self._pfb = None
+        self.solve_count += 1  # (autograd.py: the derivatives of the solve before the set are gone)
+
+    def table_values(self):
+        """The value rows in effect, (4, n_table) in TABLE_ROW_NAMES order."""
+        out = np.empty((len(TABLE_ROW_NAMES), self._tab.shape[1]))
+        for r in range(out.shape[0]):
+            check(lib().ltompc_get_table_values(self._h, r, dptr(out[r])))
+        return out
 
     # ---- per-instance vehicle and cost parameters (ltompc_set_instance_params, DESIGN.md §10) ----------------------------
     def set_theta(self, theta):
@@ -539,6 +606,28 @@ def _theta_rows(theta, B, base):
     return rows
 
 
+def _table_row(row):
+    """index of a value row (set_table_values) from its name or index"""
+    if isinstance(row, str):
+        if row not in TABLE_ROW_NAMES:
+            raise ValueError(f"set_table_values: unknown row {row!r} (one of {TABLE_ROW_NAMES})")
+        return TABLE_ROW_NAMES.index(row)
+    r = int(row)
+    if not 0 <= r < len(TABLE_ROW_NAMES):
+        raise ValueError(f"set_table_values: row must be in 0 .. {len(TABLE_ROW_NAMES) - 1} ({TABLE_ROW_NAMES}), got {row!r}")
+    return r
+
+
+def _table_values(values, n):
+    """(n,) float64 values of one table row; shape and values are checked here, before any call."""
+    v = np.array(values, dtype=np.float64, order="C", copy=True)
+    if v.shape != (n,):
+        raise ValueError(f"set_table_values: values must have shape ({n},), got {v.shape}")
+    if not np.isfinite(v).all():
+        raise ValueError(f"set_table_values: non-finite value at knot {int(np.argwhere(~np.isfinite(v))[0][0])}")
+    return v
+
+
 class SplitMPC:
     """The batch as `n_parts` handles of batch / n_parts instances, each on its own HIP stream and driven by its own host thread
     (ctypes releases the GIL during a call).  Instances are independent NLPs, so the parts need not tick together: while one
@@ -562,6 +651,7 @@ class SplitMPC:
             self.bounds.append((lo, hi)); lo = hi
         self.parts = [BatchedMPC(tables, n_horizon, hi - lo, params=params, options=options, device=device) for lo, hi in self.bounds]
         self.options, self.params = self.parts[0].options, self.parts[0].params
+        self.n_table = self.parts[0].n_table
         # three or more parts beside each other: their one-instance workgroups queue for the same CUs, so the parts switch to the
         # one-instance kernels later (ltompc_set_narrow_width; scheduling only, same bits): 128 instead of 512, +2 % with four parts
         if narrow_width is None and self.n_parts >= 3:
@@ -660,6 +750,22 @@ class SplitMPC:
     def instance_theta(self):
         return np.concatenate([p.instance_theta() for p in self.parts])
 
+    def set_table_values(self, row, values):
+        """BatchedMPC.set_table_values on every part (row and values checked first: a bad set changes no part)."""
+        r, v = _table_row(row), _table_values(values, self.n_table)
+        for p in self.parts:
+            p.set_table_values(r, v)
+
+    def set_table_values_dev(self, row, values_ptr: int):
+        """BatchedMPC.set_table_values_dev on every part: each copies the same (n_table,) device array on its own stream."""
+        r = _table_row(row)
+        for p in self.parts:
+            p.set_table_values_dev(r, values_ptr)
+
+    def table_values(self):
+        """The value rows in effect (every part holds the same ones): those of the first part."""
+        return self.parts[0].table_values()
+
     def sensitivities(self, trajectory: bool = False):
         """BatchedMPC.sensitivities of every part, stitched in the caller's order."""
         r = [p.sensitivities(trajectory) for p in self.parts]
@@ -697,6 +803,35 @@ class SplitMPC:
             p.adjoint_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0,
                           grad_p_ptr + 8 * 10 * lo if grad_p_ptr else 0, grad_theta_ptr + 8 * NTHETA * lo if grad_theta_ptr else 0,
                           ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def adjoint_tables(self, gX=None, gU=None, slots: bool = False):
+        """BatchedMPC.adjoint_tables of every part with its rows of the cotangents: grad_tables summed over the parts in part
+        order (on the host), slot_grad and ok stitched in the caller's order."""
+        gX = None if gX is None else np.asarray(gX, dtype=np.float64)
+        gU = None if gU is None else np.asarray(gU, dtype=np.float64)
+        r = [p.adjoint_tables(None if gX is None else gX[lo:hi], None if gU is None else gU[lo:hi], slots)
+             for p, (lo, hi) in zip(self.parts, self.bounds)]
+        out = dict(r[0], ok=np.concatenate([q["ok"] for q in r]))
+        gt = r[0]["grad_tables"].copy()
+        for q in r[1:]:
+            gt += q["grad_tables"]
+        out["grad_tables"] = gt
+        if slots:
+            out["slot_grad"] = np.concatenate([q["slot_grad"] for q in r])
+        return out
+
+    def adjoint_tables_dev(self, gX_ptr: int, gU_ptr: int, grad_tables_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.adjoint_tables_dev with the same arrays: slot_grad (B,N,10) and ok (B,) by rows, each part on its own
+        stream, and grad_tables (4,n_table) summed over the parts in part order: the first part overwrites the array, every
+        later one adds to it after the part before it has finished (the handle is synchronised in between, so the sum is the
+        same from call to call up to each part's own atomic order).  Returns with the parts' work enqueued or done."""
+        N = self.N
+        for i, (p, (lo, hi)) in enumerate(zip(self.parts, self.bounds)):
+            if i and grad_tables_ptr:
+                self.parts[i - 1].synchronize()
+            p.adjoint_tables_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0, grad_tables_ptr,
+                                 slot_grad_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if slot_grad_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0,
+                                 add=i > 0)
 
     def jvp(self, dp=None, dtheta=None):
         """BatchedMPC.jvp of every part with its rows of the directions, stitched in the caller's order."""
