@@ -580,6 +580,56 @@ int ltompc_get_loop_sensitivities(ltompc_handle h, double* dx_dq, double* du_dq,
 int ltompc_loop_sensitivities_dev(ltompc_handle h, double* dx_dq_dev, double* du_dq_dev, int* ok_dev);
 int ltompc_loop_end(ltompc_handle h);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Per-instance control of the warm start.  A handle carries a warm start per instance from solve to solve;
+ * ltompc_set_initial_guess throws away that of the whole batch.  The calls below act on chosen instances: every other
+ * instance keeps its warm start to the bit, and a handle on which none of them is made runs exactly as before.
+ * Instance indices, masks and rows are in the CALLER's order whatever order the handle keeps its instances in.
+ * Every call has a host form (host pointers, checked, returns when done; a usage error leaves the handle unchanged) and a
+ * _dev form (device pointers, enqueues only, on the handle's stream, NOT checked).
+ * A call that changes an instance discards the cached derivatives of the last solve (as ltompc_set_initial_guess: a derivative
+ * request before the next solve is a usage error).  Between ltompc_loop_begin and ltompc_loop_end the changing calls
+ * (reset_instances, set_guess, import_state) are usage errors: the loop's chain of an instance would be broken.
+ *
+ * ltompc_reset_instances: a cold start of the instances b with mask[b] != 0, from x0[b] (mask: batch ints, x0: batch x 8; rows
+ *   with mask 0 are ignored, also by the checks).  The iterate of a reset instance is filled as ltompc_set_initial_guess fills
+ *   it (ltompc_get_iterate shows it), its u_prev becomes 0, its previous status, node-0 flag and sticky / restoration counters
+ *   are cleared, and its next solve (make_step, make_step_dev, or its first one in rollout_dev) is a cold solve, bit for bit the
+ *   first solve of a fresh handle.  A ltompc_set_u_prev after the reset overrides the zero for that solve; one before it is
+ *   zeroed for the reset instances.  With options.warm_shift a reset instance is simply cold.  An all-ones mask is
+ *   ltompc_set_initial_guess; an all-zeros mask changes nothing.
+ *
+ * ltompc_set_guess: a primal starting point for the instances with mask[b] != 0, in the layouts of ltompc_get_iterate:
+ *   X batch x (N+1) x 8, C batch x N x 8 (the collocation states; e.g. x_k + (x_{k+1} - x_k) / 3, the Radau point at tau = 1/3),
+ *   U batch x N x 2, u_prev batch x 2 or NULL (= 0).  The guess stands in for a previous solution that did not converge:
+ *   planes := guess, L1 = L2 = 0, previous status := LTOMPC_STATUS_MAX_ITER, node-0 flag and sticky counters cleared, NOT
+ *   cold.  Everything else is what the start of a solve does after a failed one: node 0 := the measured x0, barrier at mu_init
+ *   (options.warm_reset_on_fail), slacks from the point; every warm-start option applies to the guess as to a previous solution.
+ *   The host form refuses non-finite entries in the rows it uses.
+ *
+ * ltompc_warm_state_size: doubles per instance of a blob row (34 N + 18).
+ * ltompc_export_state / ltompc_import_state: blob is n x size doubles, row j = instance idx[j] (idx NULL: instance j, n <= batch).
+ *   A row holds everything the instance's next solve depends on: a header word (magic, layout version, N), the previous
+ *   status, node-0 flag, restoration / sticky counters and the pending-cold flag, u_prev, and the planes X, C, U, L1, L2.
+ *   NOT part of it: per-instance parameter rows (ltompc_set_instance_params) and the tables, which the caller sets on the
+ *   target as on the source.  A blob is valid between handles of equal N, options and library build (only N and the layout
+ *   version are checked).  After an import the iterate and prediction accessors show the imported point (T and NU of
+ *   ltompc_get_ineq are rebuilt by the next solve); ltompc_get_stats shows the imported status; the other per-solve statistics
+ *   (iters, kkt_error, counters, restoration, recovery) stay what they were until the next solve.
+ *   Host-form usage errors: an index out of range, an index twice in an import, a wrong header, a non-finite payload (the
+ *   planes of a row that starts cold are not looked at).  Export changes nothing and is allowed inside an open loop.
+ * Returns 0 (ltompc_warm_state_size: the size), or < 0 with ltompc_last_error(). */
+int ltompc_reset_instances(ltompc_handle h, const int* mask, const double* x0);
+int ltompc_reset_instances_dev(ltompc_handle h, const int* mask_dev, const double* x0_dev);
+int ltompc_set_guess(ltompc_handle h, const int* mask, const double* X, const double* C, const double* U, const double* u_prev);
+int ltompc_set_guess_dev(ltompc_handle h, const int* mask_dev, const double* X_dev, const double* C_dev, const double* U_dev,
+                         const double* u_prev_dev);
+int ltompc_warm_state_size(ltompc_handle h);
+int ltompc_export_state(ltompc_handle h, const int* idx, int n, double* blob);
+int ltompc_export_state_dev(ltompc_handle h, const int* idx_dev, int n, double* blob_dev);
+int ltompc_import_state(ltompc_handle h, const int* idx, int n, const double* blob);
+int ltompc_import_state_dev(ltompc_handle h, const int* idx_dev, int n, const double* blob_dev);
+
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:
  * index 0 eval (k_eval or k_eval8), 1 riccati (8 instances per wavefront), 2 expand (k_expand or k_expand8), 3 linesearch,

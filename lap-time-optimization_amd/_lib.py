@@ -99,6 +99,15 @@ def lib() -> C.CDLL:
         L.ltompc_get_loop_sensitivities.argtypes = [C.c_void_p, _dp, _dp, _ip, _ip]
         L.ltompc_loop_sensitivities_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_loop_end.argtypes = [C.c_void_p]
+        L.ltompc_reset_instances.argtypes = [C.c_void_p, _ip, _dp]
+        L.ltompc_reset_instances_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_set_guess.argtypes = [C.c_void_p, _ip, _dp, _dp, _dp, _dp]
+        L.ltompc_set_guess_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_warm_state_size.argtypes = [C.c_void_p]
+        L.ltompc_export_state.argtypes = [C.c_void_p, _ip, C.c_int, _dp]
+        L.ltompc_export_state_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ltompc_import_state.argtypes = [C.c_void_p, _ip, C.c_int, _dp]
+        L.ltompc_import_state_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 

@@ -36,6 +36,10 @@
 //                 values of the track tables (ltompc_get_adjoint_tables): adjoint.h's recursion keeping its trajectory,
 //                 the per-slot contraction with the condensed columns of the ten look-up results, the scatter to the knots (lut_basis)
 //   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the six headers above
+//   warm_state.h  per-instance control of the warm start: k_load_x0_m / k_init_m / k_roll_mark_m / k_roll_init_m (the
+//                 start of a solve with a per-instance cold flag), k_ws_reset_* (ltompc_reset_instances), k_ws_guess (ltompc_set_guess),
+//                 k_ws_export / k_ws_import (the carried state of chosen instances <-> instance-major blobs, an LDS tile transpose)
+//   warm_state_host.h (host, part of ltompc.hip only) their C entry points
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
@@ -54,3 +58,4 @@
 #include "jvp.h"
 #include "plant_sensitivity.h"
 #include "table_sensitivity.h"
+#include "warm_state.h"

@@ -93,6 +93,12 @@ struct ltompc_solver {
   bool packing = true;  // LTOMPC_PACK=0: re-pack the list of unfinished instances only, leave their data where it is
   std::vector<int> history;  // (iteration, n_active, n_launch) triples of the last make_step's polls
   bool cold_next = true;
+  // per-instance control of the warm start (warm_state.h).  d_cold: the "starts cold" flag of every instance, in
+  // the caller's order, allocated by the first of those calls; cold_pending: a flag may be set, the start of the next solve reads
+  // them (and clears them).  cold_pending implies !cold_next: the calls turn the handle-wide flag into every instance's.
+  int *d_cold = nullptr, *d_inv = nullptr, *d_ws_int = nullptr;  // d_inv: caller's index -> slot; d_ws_int, d_ws_stage: staging of the host forms
+  double* d_ws_stage = nullptr;
+  bool cold_pending = false;
   bool uprev_set = false;  // ltompc_set_u_prev since the last solve or initial guess: the next solve's cold start keeps W.uprev
   bool after_rollout = false;  // the last solve was a rollout: W.active holds no per-iteration counts
   int poll_every = 4;
@@ -427,6 +433,7 @@ int via_io(ltompc_solver* h, const double* x, const double* u, double* x_next, c
 }  // namespace
 
 #include "deriv_passes.h"
+#include "warm_state_host.h"
 
 extern "C" {
 
@@ -696,6 +703,10 @@ int ltompc_set_initial_guess_dev(ltompc_handle h, const double* x0_dev) {
   hipLaunchKernelGGL(k_init, dim3((h->N * h->Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, 1);
   HIPCHECK(hipGetLastError());
   h->cold_next = true;  // the next make_step starts from this guess
+  if (h->cold_pending) {  // (every instance starts cold: the single flags have nothing left to say)
+    HIPCHECK(hipMemsetAsync(h->d_cold, 0, sizeof(int) * h->Bp, h->stream));
+    h->cold_pending = false;
+  }
   h->uprev_set = false;  // (a u_prev set before the guess is gone with the rest)
   return 0;
 }
@@ -787,6 +798,9 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
   Launcher L{h};
   h->dv.discard();
   if (commit_theta(h)) return -1;
+  const bool per_inst = h->cold_pending;  // cold or warm per instance (warm_state.h): the same device functions, each instance's own flag
+  if (per_inst) hipLaunchKernelGGL(k_load_x0_m, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, h->K.o.resto_sticky, (const int*)h->d_cold);
+  else
   hipLaunchKernelGGL(k_load_x0, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, x0_dev, (const int*)(h->packed ? h->d_orig : nullptr),
                      h->K.o.resto_sticky, h->cold_next ? 0 : 1);
   if (h->cold_next && !h->uprev_set) hipLaunchKernelGGL(k_zero_uprev, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W);
@@ -795,7 +809,12 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 0);
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 1);
   }
-  if (h->pi_solve) hipLaunchKernelGGL(k_init_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, h->cold_next ? 1 : 0);
+  if (per_inst) {
+    if (h->pi_solve) hipLaunchKernelGGL(k_init_m_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, (const int*)h->d_cold);
+    else hipLaunchKernelGGL(k_init_m, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, (const int*)h->d_cold);
+    HIPCHECK(hipMemsetAsync(h->d_cold, 0, sizeof(int) * Bp, h->stream));
+    h->cold_pending = false;
+  } else if (h->pi_solve) hipLaunchKernelGGL(k_init_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, h->cold_next ? 1 : 0);
   else hipLaunchKernelGGL(k_init, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, h->cold_next ? 1 : 0);
   HIPCHECK(hipMemsetAsync(h->W.active, 0, sizeof(int) * ((size_t)h->max_iter + 2), h->stream));
   HIPCHECK(hipMemsetAsync(h->W.ls_count, 0, 2 * sizeof(int), h->stream));
@@ -1000,11 +1019,19 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
     int* const d_list = h->d_plist + (size_t)slot * Bp;
     if (done_pending[slot]) ROLLCHECK(hipStreamWaitEvent(h->stream, h->ev_done[slot], 0));  // (the plant kernel that read this slot's list, RING passes ago)
     ROLLCHECK(hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), h->stream));
+    if (first && h->cold_pending) {  // cold or warm per instance (warm_state.h), in the first pass: every instance starts its first solve there
+      hipLaunchKernelGGL(k_roll_mark_m, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, (const double*)x_dev, h->K.o.resto_sticky, (const int*)h->d_cold);
+      if (h->pi_solve) hipLaunchKernelGGL(k_roll_init_m_pi, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, la, (const int*)h->d_cold);
+      else hipLaunchKernelGGL(k_roll_init_m, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, la, (const int*)h->d_cold);
+      ROLLCHECK(hipMemsetAsync(h->d_cold, 0, sizeof(int) * Bp, h->stream));
+      h->cold_pending = false;
+    } else {
     hipLaunchKernelGGL(k_roll_mark, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, (const double*)x_dev, h->K.o.resto_sticky,
                        (first && h->cold_next) ? 1 : 0);  // (after set_initial_guess there is no solve before this one to take stock of)
     if (h->pi_solve)
       hipLaunchKernelGGL(k_roll_init_pi, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, la, (first && h->cold_next) ? 1 : 0);
     else hipLaunchKernelGGL(k_roll_init, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, la, (first && h->cold_next) ? 1 : 0);
+    }
     la.force_eval = 0;
     if (launch_iteration(h, L, la, -1, n_launch, ls_width, ell, false) < 0) { rc = -1; break; }  // (-1: no per-iteration count of unfinished instances, a make_step facility)
     hipLaunchKernelGGL(k_roll_finish, dim3((np + 63) / 64), dim3(64), 0, h->stream, h->W, la, u_log_dev, status_log_dev, iters_log_dev, n_ticks,

@@ -124,6 +124,93 @@ class BatchedMPC:
     def plant_step_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int, n_sub: int = 400):
         check(lib().ltompc_plant_step_dev(self._h, C.c_void_p(x_ptr), C.c_void_p(u_ptr), int(n_sub), C.c_void_p(xn_ptr)))
 
+    # ---- per-instance control of the warm start (ltompc_reset_instances, ...) ----------------------------------
+    def _instances_changed(self, rows=None, u_prev=None):
+        """After a call that changed the iterate of some instances: no solve to expand around or to differentiate
+        (solve_count: autograd.py refuses the graph of the solve before it), and the next solve's u_prev of `rows` is
+        u_prev (None: the host does not see it any more)."""
+        self._solved = None
+        self._fb = self._pfb = None
+        self.solve_count += 1
+        if rows is None or u_prev is None or self._uprev_next is None:
+            self._uprev_next = None
+        else:
+            self._uprev_next[rows] = u_prev
+
+    def reset(self, mask, x0):
+        """Cold-start the instances where mask (B,) is true from x0 (B,8; the other rows are ignored): their next solve is bit
+        for bit the first solve of a fresh handle (u_prev 0, no previous status, counters cleared); every other instance
+        keeps its warm start to the bit.  iterate() shows the guess.  ltompc_reset_instances."""
+        m, x0 = _mask(mask, self.B), self._x(x0)
+        check(lib().ltompc_reset_instances(self._h, iptr(m), dptr(x0)))
+        self._instances_changed(m != 0, 0.0)
+
+    def reset_dev(self, mask_ptr: int, x0_ptr: int):
+        """reset from device arrays of (B,) int32 and (B,8) float64: enqueued on the handle's stream, NOT checked."""
+        check(lib().ltompc_reset_instances_dev(self._h, C.c_void_p(mask_ptr), C.c_void_p(x0_ptr)))
+        self._instances_changed()
+
+    def set_guess(self, mask, X, U, C=None, u_prev=None):
+        """A primal starting point for the instances where mask (B,) is true: X (B,N+1,8), U (B,N,2), C (B,N,8) collocation
+        states (None: x_k + (x_{k+1} - x_k) / 3, the Radau point at tau = 1/3), u_prev (B,2) or None (= 0).  The guess stands
+        in for a previous solution that did not converge (status MAX_ITER, multipliers 0): the next solve warm-starts from it
+        under the handle's warm-start options.  ltompc_set_guess."""
+        B, N = self.B, self.N
+        m = _mask(mask, B)
+        X = _shaped("set_guess", "X", X, (B, N + 1, NX))
+        U = _shaped("set_guess", "U", U, (B, N, NU))
+        Cc = guess_collocation(X) if C is None else _shaped("set_guess", "C", C, (B, N, NX))
+        up = None if u_prev is None else _shaped("set_guess", "u_prev", u_prev, (B, NU))
+        check(lib().ltompc_set_guess(self._h, iptr(m), dptr(X), dptr(Cc), dptr(U), dptr(up) if up is not None else None))
+        self._instances_changed(m != 0, 0.0 if up is None else up[m != 0])
+
+    def set_guess_dev(self, mask_ptr: int, X_ptr: int, C_ptr: int, U_ptr: int, u_prev_ptr: int = 0):
+        """set_guess from device arrays (C is always given): enqueued on the handle's stream, NOT checked."""
+        check(lib().ltompc_set_guess_dev(self._h, C.c_void_p(mask_ptr), C.c_void_p(X_ptr), C.c_void_p(C_ptr), C.c_void_p(U_ptr),
+                                         C.c_void_p(u_prev_ptr or None)))
+        self._instances_changed()
+
+    @property
+    def warm_state_size(self) -> int:
+        """Doubles per instance of an export_state() row."""
+        n = lib().ltompc_warm_state_size(self._h)
+        if n < 0:
+            check(n)
+        return int(n)
+
+    def export_state(self, idx=None):
+        """The warm start of the instances idx (None: all, in order) as a (n, warm_state_size) array: everything their next
+        solve depends on (planes X, C, U, L1, L2, u_prev, previous status, counters, the pending-cold flag), not the theta
+        rows and tables.  Valid for import_state on handles of equal N, options and library build.  ltompc_export_state."""
+        ix = _indices(idx, self.B, unique=False)
+        n = self.B if ix is None else ix.size
+        blob = np.empty((n, self.warm_state_size))
+        check(lib().ltompc_export_state(self._h, iptr(ix) if ix is not None else None, n, dptr(blob)))
+        return blob
+
+    def export_state_dev(self, idx_ptr: int, n: int, blob_ptr: int):
+        """export_state into a device array (n, warm_state_size) for a device list of n int32 indices (0: the first n
+        instances): enqueued on the handle's stream."""
+        check(lib().ltompc_export_state_dev(self._h, C.c_void_p(idx_ptr or None), int(n), C.c_void_p(blob_ptr)))
+
+    def import_state(self, blob, idx=None):
+        """Make the rows of an export_state() array the warm start of the instances idx (None: instance j from row j; no index
+        twice): their next solve is bit for bit the one the exporting instance would have made.  iterate() / prediction()
+        show the imported point; the per-solve statistics stay those of the slot's last solve.  ltompc_import_state."""
+        ix = _indices(idx, self.B, unique=True)
+        blob = np.ascontiguousarray(blob, dtype=np.float64)
+        n = blob.shape[0] if blob.ndim == 2 else -1
+        if blob.ndim != 2 or blob.shape[1] != self.warm_state_size or (ix is not None and ix.size != n) or n > self.B:
+            raise ValueError(f"import_state: blob must be (n <= {self.B}, {self.warm_state_size}) with one row per index, got {blob.shape}")
+        check(lib().ltompc_import_state(self._h, iptr(ix) if ix is not None else None, n, dptr(blob)))
+        self._instances_changed(np.arange(n) if ix is None else ix, blob[:, WS_UPREV:WS_UPREV + NU])
+
+    def import_state_dev(self, idx_ptr: int, n: int, blob_ptr: int):
+        """import_state from a device array (n, warm_state_size) and a device list of n distinct int32 indices (0: the first n
+        instances): enqueued on the handle's stream, NOT checked."""
+        check(lib().ltompc_import_state_dev(self._h, C.c_void_p(idx_ptr or None), int(n), C.c_void_p(blob_ptr)))
+        self._instances_changed()
+
     # ---- parametric sensitivities (ltompc_get_sensitivities, DESIGN.md §9) -----------------------
     def sensitivities(self, trajectory: bool = False):
         """Derivatives of the last solve's solution w.r.t. p = (x0, u_prev), at its final iterate (include/ltompc.h).
@@ -577,6 +664,43 @@ class BatchedMPC:
         return x0
 
 
+WS_UPREV = 7  # column of u_prev in a row of export_state() (csrc/warm_state.h)
+
+
+def guess_collocation(X):
+    """The collocation states of a guess from its node states X (..., N+1, 8): x_k + (x_{k+1} - x_k) / 3, the Radau point at
+    tau = 1/3 on the straight line between two nodes."""
+    X = np.asarray(X, dtype=np.float64)
+    return np.ascontiguousarray(X[..., :-1, :] + (X[..., 1:, :] - X[..., :-1, :]) / 3.0)
+
+
+def _mask(mask, B):
+    """(B,) int32 0/1 from a boolean or integer mask; the shape is checked here, before any call."""
+    m = np.asarray(mask)
+    if m.shape != (B,):
+        raise ValueError(f"mask must have shape ({B},), got {m.shape}")
+    return np.ascontiguousarray(m != 0, dtype=np.int32)
+
+
+def _indices(idx, B, unique):
+    """int32 instance indices (None stays None: all, in order); range and, for an import, uniqueness are checked here."""
+    if idx is None:
+        return None
+    ix = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+    if ix.size and (ix.min() < 0 or ix.max() >= B):
+        raise ValueError(f"instance index out of range [0, {B})")
+    if unique and np.unique(ix).size != ix.size:
+        raise ValueError("an instance index appears twice")
+    return ix.astype(np.int32)
+
+
+def _shaped(who, name, a, shape):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"{who}: {name} must have shape {shape}, got {a.shape}")
+    return a
+
+
 _DEV_ROWS = object()  # BatchedMPC._theta_rows after set_theta_dev: the rows are in device memory only
 
 
@@ -737,6 +861,73 @@ class SplitMPC:
     def iterate(self):
         r = [p.iterate() for p in self.parts]
         return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    # ---- per-instance control of the warm start: masks and global indices split across the parts, parts with nothing to do skipped
+    def reset(self, mask, x0):
+        """BatchedMPC.reset with the rows split across the parts."""
+        m = _mask(mask, self.B)
+        x0 = np.asarray(x0, dtype=np.float64).reshape(-1, NX)
+        if x0.shape[0] != self.B:
+            raise ValueError(f"reset: expected {self.B} states of dimension {NX}, got array of shape {x0.shape}")
+        if not np.isfinite(x0[m != 0]).all():  # (the whole batch checked first: a bad row changes no part)
+            raise ValueError("reset: non-finite x0 in a masked row")
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            if m[lo:hi].any():
+                p.reset(m[lo:hi], x0[lo:hi])
+
+    def reset_dev(self, mask_ptr: int, x0_ptr: int):
+        """BatchedMPC.reset_dev of every part on its rows of (B,) int32 / (B,8) doubles, each on its part's stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.reset_dev(mask_ptr + 4 * lo, x0_ptr + 8 * NX * lo)
+
+    def set_guess(self, mask, X, U, C=None, u_prev=None):
+        """BatchedMPC.set_guess with the rows split across the parts."""
+        B, N = self.B, self.N
+        m = _mask(mask, B)
+        X, U = _shaped("set_guess", "X", X, (B, N + 1, NX)), _shaped("set_guess", "U", U, (B, N, NU))
+        Cc = guess_collocation(X) if C is None else _shaped("set_guess", "C", C, (B, N, NX))
+        up = None if u_prev is None else _shaped("set_guess", "u_prev", u_prev, (B, NU))
+        on = m != 0
+        if not (np.isfinite(X[on]).all() and np.isfinite(U[on]).all() and np.isfinite(Cc[on]).all() and (up is None or np.isfinite(up[on]).all())):
+            raise ValueError("set_guess: non-finite entry in a masked row")  # (checked first: a bad row changes no part)
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            if m[lo:hi].any():
+                p.set_guess(m[lo:hi], X[lo:hi], U[lo:hi], Cc[lo:hi], None if up is None else up[lo:hi])
+
+    def set_guess_dev(self, mask_ptr: int, X_ptr: int, C_ptr: int, U_ptr: int, u_prev_ptr: int = 0):
+        """BatchedMPC.set_guess_dev of every part on its rows, each on its part's stream."""
+        N = self.N
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.set_guess_dev(mask_ptr + 4 * lo, X_ptr + 8 * (N + 1) * NX * lo, C_ptr + 8 * N * NX * lo, U_ptr + 8 * N * NU * lo,
+                            u_prev_ptr + 8 * NU * lo if u_prev_ptr else 0)
+
+    @property
+    def warm_state_size(self) -> int:
+        return self.parts[0].warm_state_size
+
+    def _by_part(self, ix):
+        """(part, rows of the list, the part's own indices) for the parts that own an index of the global list ix."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            rows = np.flatnonzero((ix >= lo) & (ix < hi))
+            if rows.size:
+                yield p, rows, ix[rows] - lo
+
+    def export_state(self, idx=None):
+        """BatchedMPC.export_state by global index: row j = instance idx[j] of the whole batch (None: all, in order)."""
+        ix = np.arange(self.B, dtype=np.int32) if idx is None else _indices(idx, self.B, unique=False)
+        blob = np.empty((ix.size, self.warm_state_size))
+        for p, rows, local in self._by_part(ix):
+            blob[rows] = p.export_state(local)
+        return blob
+
+    def import_state(self, blob, idx=None):
+        """BatchedMPC.import_state by global index (a blob row may come from any part, or from a BatchedMPC)."""
+        blob = np.asarray(blob, dtype=np.float64)
+        ix = np.arange(blob.shape[0], dtype=np.int32) if idx is None else _indices(idx, self.B, unique=True)
+        if blob.ndim != 2 or blob.shape != (ix.size, self.warm_state_size) or ix.size > self.B:
+            raise ValueError(f"import_state: blob must be (n <= {self.B}, {self.warm_state_size}) with one row per index, got {blob.shape}")
+        for p, rows, local in self._by_part(ix):
+            p.import_state(blob[rows], local)
 
     def set_theta(self, theta):
         """BatchedMPC.set_theta with the rows split across the parts (a (B, 16) array, a dict of scalars / (B,) arrays, or None)."""
