@@ -513,6 +513,50 @@ int ltompc_set_table_values(ltompc_handle h, int row, const double* values);
 int ltompc_set_table_values_dev(ltompc_handle h, int row, const double* values_dev);
 int ltompc_get_table_values(ltompc_handle h, int row, double* values);
 
+/* Per-instance table sets.  A handle may hold n_sets >= 1 table sets - each the LTOMPC_TABLE_VALUE_ROWS value
+ * rows (kappa, n_left, n_right, v_ref, n_table doubles each) on the handle's own two grids - and an index set_of_instance[batch]
+ * in the caller's instance order.  Instance b's solve, plant step, rollout and supported derivative passes are then bit for bit
+ * those of a handle created with the handle's tables, options and params and set set_of_instance[b] written into the value rows
+ * (a twin in thread-per-slot evaluation mode, latency_mode = 2: handles with sets run the thread-per-slot evaluation kernels
+ * whatever latency_mode says, as friction-ellipse handles do).  The grids, n_table, the period and the interval estimates stay
+ * the handle's.  While sets are in effect no instance reads the handle's own value rows; ltompc_set_table_values keeps writing
+ * them, and they take effect again once the sets are dropped.
+ *
+ * ltompc_set_table_sets: host pointers.  values is n_sets x 4 x n_table, set_of_instance is batch ints.
+ *   values == NULL with n_sets unchanged changes the index only (the common move of a population method);
+ *   set_of_instance == NULL keeps the index (all zeros before the first one; a usage error when it was written for more sets);
+ *   n_sets == 0 goes back to the handle's tables (both pointers are ignored).
+ *   A non-finite value is a usage error that names the set, an index outside [0, n_sets) one that names the instance; either
+ *   leaves the handle unchanged.  A handle with ell_penalty > 0 or ptv != 0 and the debug path LTOMPC_RICCATI=serial refuse sets.
+ * ltompc_set_table_sets_dev: the same from device arrays, enqueued on the handle's stream.  The values are NOT checked; the index
+ *   is clamped into [0, n_sets) by the kernel that copies it, so no look-up can leave the value buffer.  The first set of either
+ *   kind, and every set with more sets than the handle ever held, allocates and synchronises once.
+ * ltompc_get_table_sets: n_sets in effect (0: none; then nothing else is written), and the values and the index in effect (host,
+ *   out; either may be NULL), after everything enqueued on the handle's stream before it.
+ *
+ * Timing is ltompc_set_table_values' contract: a set takes effect from the next solve, plant step and rollout; the warm start is
+ * kept (so are the per-instance rows); the derivative state of the last solve is discarded until the next solve.  One device
+ * buffer each for the values and the index.  The warm-state blobs (ltompc_export_warm_state) do not carry the set index.
+ *
+ * With sets in effect these run: make_step(_dev), plant_step(_dev), rollout_dev, the prediction and iterate accessors,
+ * ltompc_get_sensitivities / ltompc_sensitivities_dev, ltompc_get_adjoint(_dev) without grad_theta, ltompc_get_jvp(_dev) with dp
+ * only, the per-set table gradient below, and the calls of the warm-start control.  These are usage errors: the derivatives
+ * w.r.t. theta (ltompc_get_param_sensitivities, grad_theta, dtheta), ltompc_plant_sensitivities, the ltompc_loop_* calls and
+ * the handle-wide ltompc_get_adjoint_tables / ltompc_adjoint_tables(_add)_dev (which point to the calls below).
+ *
+ * ltompc_get_adjoint_table_sets, ltompc_adjoint_table_sets_dev, ltompc_adjoint_table_sets_add_dev: ltompc_get_adjoint_tables and
+ * its two _dev forms with grad_sets [n_sets][4][n_table] in place of grad_tables: block g is summed over the ok instances of
+ * set g (a set without instances gets zeros).  slot_grad and ok are as there.  On a handle without sets they are a usage error
+ * that points to the handle-wide calls. */
+int ltompc_set_table_sets(ltompc_handle h, int n_sets, const double* values, const int* set_of_instance);
+int ltompc_set_table_sets_dev(ltompc_handle h, int n_sets, const double* values_dev, const int* set_of_instance_dev);
+int ltompc_get_table_sets(ltompc_handle h, int* n_sets, double* values, int* set_of_instance);
+int ltompc_get_adjoint_table_sets(ltompc_handle h, const double* gX, const double* gU, double* grad_sets, double* slot_grad, int* ok);
+int ltompc_adjoint_table_sets_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_sets_dev, double* slot_grad_dev,
+                                  int* ok_dev);
+int ltompc_adjoint_table_sets_add_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_sets_dev,
+                                      double* slot_grad_dev, int* ok_dev);
+
 /* Per-instance vehicle and cost parameters.  Instance b may have its own row theta_b: the LTOMPC_NTHETA = 16
  * values of ltompc_get_param_sensitivities' columns, in that order and in natural units.  Every other field of ltompc_params
  * stays the handle's.  Instance b's NLP, plant step and sensitivities are then bit for bit those of a handle created with

@@ -88,6 +88,12 @@ def lib() -> C.CDLL:
         L.ltompc_set_table_values.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ltompc_set_table_values_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.ltompc_get_table_values.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.ltompc_set_table_sets.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
+        L.ltompc_set_table_sets_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ltompc_get_table_sets.argtypes = [C.c_void_p, _ip, _dp, _ip]
+        L.ltompc_get_adjoint_table_sets.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
+        L.ltompc_adjoint_table_sets_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_adjoint_table_sets_add_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_set_instance_params.argtypes = [C.c_void_p, _dp]
         L.ltompc_set_instance_params_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_get_instance_params.argtypes = [C.c_void_p, _dp]

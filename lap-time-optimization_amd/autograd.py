@@ -59,6 +59,9 @@ class _Solve(torch.autograd.Function):
         _check(mpc, "mpc_solve: x0", x0, (B, NX))
         if tables is not None:
             _check(mpc, "mpc_solve: tables", tables, (NROWS, mpc.n_table))  # (the handle copies n_table doubles per row)
+            if getattr(mpc, "n_table_sets", 0):
+                raise RuntimeError("mpc_solve: `tables` is the handle-wide table input and this handle has per-instance table sets "
+                                   "(set_table_sets): no instance reads the handle's rows; adjoint_table_sets_dev gives one gradient per set")
         if u_prev is not None:
             _check(mpc, "mpc_solve: u_prev", u_prev, (B, NU))
         if theta is not None:

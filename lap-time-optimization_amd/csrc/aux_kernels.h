@@ -7,7 +7,7 @@ namespace ltompc {
 // ------------------------------------------------------------------------------------------ k_init
 // Cold: do_mpc set_initial_guess (every state slot = x0, inputs 0, multipliers 0).  Warm: keep the previous
 // primal/dual solution un-shifted (do_mpc), node 0 := new x0.  Slacks t = max(-h, bound_push), nu = mu/t.
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_init_slot(const Consts& K, const Work& W, const int k, const int b, const int cold) {
   const int N = W.N;
   double x0[8];
@@ -58,7 +58,7 @@ __device__ __forceinline__ void d_init_slot(const Consts& K, const Work& W, cons
   const double eps = (K.o.smooth_scale > 0 || K.o.smooth_eps_min > 0) ? fmax(K.o.smooth_eps_min, K.o.smooth_scale * mu_s) : 0.0;
   const double rho = inf_sticky ? fmax(K.o.resto_rho, K.o.resto_rho_max) : (start_elastic ? K.o.resto_rho : K.o.soft_rho);  // (the restoration phase replaces it per instance, see d_pick)
   const double mu = mu_s * pen_scale(rho);  // (penalty scale, layout.h: 1 unless rho > RHO_UNIT)
-  init_slot_slacks<BoundsAny>(K, W, k, b, mu, eps, rho, xp, c, u);
+  init_slot_slacks<BoundsAny, TS>(K, W, k, b, mu, eps, rho, xp, c, u);
   if (k == 0) {
     double* st = W.st;
     st[(size_t)ST_MU * W.Bp + b] = mu, st[(size_t)ST_EPS * W.Bp + b] = eps, st[(size_t)ST_EPS_NEXT * W.Bp + b] = eps;
@@ -67,7 +67,7 @@ __device__ __forceinline__ void d_init_slot(const Consts& K, const Work& W, cons
     st[(size_t)ST_E0 * W.Bp + b] = 1e300, st[(size_t)ST_OBJ * W.Bp + b] = 0.0, st[(size_t)ST_TAU * W.Bp + b] = 0.99;
     st[(size_t)ST_THETA0 * W.Bp + b] = -1.0, st[(size_t)ST_THMAX * W.Bp + b] = 0.0, st[(size_t)ST_THMIN * W.Bp + b] = 0.0;
     st[(size_t)ST_DW * W.Bp + b] = 0.0, st[(size_t)ST_DW_TRY * W.Bp + b] = 0.0;
-    st[(size_t)ST_C00 * W.Bp + b] = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, x0, false, nullptr, nullptr);
+    st[(size_t)ST_C00 * W.Bp + b] = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, x0, false, nullptr, nullptr);
     st[(size_t)ST_RHO * W.Bp + b] = rho, st[(size_t)ST_VIOL * W.Bp + b] = 0.0;
     for (int i = 0; i < SI_NF; i++)
       if (i != SI_PREV && (i != SI_STICKY || cold) && i != SI_PHASE && i != SI_TICKS && i != SI_FINAL) W.si[(size_t)i * W.Bp + b] = 0;
@@ -77,7 +77,7 @@ __device__ __forceinline__ void d_init_slot(const Consts& K, const Work& W, cons
     {  // options.node0_check: the track constraints at the measured state (node 0 of do_mpc's NLP), at the final smoothing
       const double eps0 = (K.o.smooth_scale > 0 || K.o.smooth_eps_min > 0) ? K.o.smooth_eps_min : 0.0;
       double g0[3];
-      cons_eval(K.p, K.T, eps0, x0, g0, nullptr, nullptr, nullptr, nullptr, nullptr);
+      cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps0, x0, g0, nullptr, nullptr, nullptr, nullptr, nullptr);
       st[(size_t)ST_G0 * W.Bp + b] = fmax(g0[0], fmax(g0[1], g0[2]));
     }
     if (start_elastic) W.si[(size_t)SI_RESTO * W.Bp + b] = 1, W.si[(size_t)SI_NRESTO * W.Bp + b] = 1, W.si[(size_t)SI_STARTEL * W.Bp + b] = 1;
@@ -99,6 +99,15 @@ __global__ void k_init_pi(const Consts* __restrict__ Kp, const WorkPI* __restric
   int b = tid % W.Bp, k = tid / W.Bp;
   if (k >= W.N || b >= W.B) return;
   d_init_slot<true>(K, W, k, b, cold);
+}
+// ... and per-instance table sets (W.TSV / W.TSI)
+__global__ void k_init_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, int cold) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int b = tid % W.Bp, k = tid / W.Bp;
+  if (k >= W.N || b >= W.B) return;
+  d_init_slot<true, true>(K, W, k, b, cold);
 }
 
 // ------------------------------------------------------------------------------------------ k_shift
@@ -290,25 +299,28 @@ __global__ void k_status_counts(Work W, int* __restrict__ counts, unsigned long 
 
 // plant: classical RK4 with n_sub sub-steps, zero-order-hold input (do_mpc Simulator / CVODES stand-in)
 // PI: the vehicle parameters of column col of the [LTOMPC_NTHETA][Bp] plane th
-template <bool PI = false, class TP = const double*>
+// TS: the value rows of set `set` of tsv
+template <bool PI = false, class TP = const double*, bool TS = false, class VP = const double*>
 __device__ __forceinline__ void d_plant(const Consts& K, const double* x, const double* uu, const double dt, const int n_sub, double* y,
-                                        const TP th = nullptr, const size_t Bp = 0, const size_t col = 0) {
+                                        const TP th = nullptr, const size_t Bp = 0, const size_t col = 0, const VP tsv = nullptr,
+                                        const int set = 0) {
   decltype(auto) p = sel_params<PI>(K.p, th, Bp, col);
+  decltype(auto) T = sel_tables<TS>(K.T, tsv, set);
 #pragma unroll
   for (int i = 0; i < 8; i++) y[i] = x[i];
   const double hs = dt / n_sub;
   for (int s = 0; s < n_sub; s++) {
     double k1[8], k2[8], k3[8], k4[8], z[8];
-    rhs_val(p, K.T, 0.0, y, uu, k1);
+    rhs_val(p, T, 0.0, y, uu, k1);
 #pragma unroll
     for (int i = 0; i < 8; i++) z[i] = y[i] + 0.5 * hs * k1[i];
-    rhs_val(p, K.T, 0.0, z, uu, k2);
+    rhs_val(p, T, 0.0, z, uu, k2);
 #pragma unroll
     for (int i = 0; i < 8; i++) z[i] = y[i] + 0.5 * hs * k2[i];
-    rhs_val(p, K.T, 0.0, z, uu, k3);
+    rhs_val(p, T, 0.0, z, uu, k3);
 #pragma unroll
     for (int i = 0; i < 8; i++) z[i] = y[i] + hs * k3[i];
-    rhs_val(p, K.T, 0.0, z, uu, k4);
+    rhs_val(p, T, 0.0, z, uu, k4);
 #pragma unroll
     for (int i = 0; i < 8; i++) y[i] += hs / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
   }
@@ -335,6 +347,28 @@ __global__ void __launch_bounds__(64) k_plant_pi(Consts K, const double* __restr
   d_plant<true>(K, xb, uu, dt, n_sub, y, th, Bp, b);
 #pragma unroll
   for (int i = 0; i < 8; i++) xn[(size_t)b * 8 + i] = y[i];
+}
+// ... and per-instance table sets: tsv [n_sets][LTOMPC_TABLE_VALUE_ROWS][n_table], tsi [Bp] in the caller's instance order
+__global__ void __launch_bounds__(64) k_plant_ts(Consts K, const double* __restrict__ th, const double* __restrict__ tsv,
+                                                 const int* __restrict__ tsi, int Bp, int B, const double* __restrict__ x,
+                                                 const double* __restrict__ u, double dt, int n_sub, double* __restrict__ xn) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double xb[8], y[8], uu[2] = {u[(size_t)b * 2], u[(size_t)b * 2 + 1]};
+#pragma unroll
+  for (int i = 0; i < 8; i++) xb[i] = x[(size_t)b * 8 + i];
+  d_plant<true, const double*, true>(K, xb, uu, dt, n_sub, y, th, Bp, b, tsv, tsi[b]);
+#pragma unroll
+  for (int i = 0; i < 8; i++) xn[(size_t)b * 8 + i] = y[i];
+}
+
+// set_of_instance (device, caller's order) -> tsi[0 .. B-1], clamped into [0, n_sets) (ltompc_set_table_sets_dev: no look-up
+// can leave the value buffer whatever the caller's array holds)
+__global__ void k_ts_index(const int* __restrict__ idx, int* __restrict__ tsi, int B, int n_sets) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int s = idx[b];
+  tsi[b] = s < 0 ? 0 : (s >= n_sets ? n_sets - 1 : s);
 }
 
 // [B][LTOMPC_NTHETA] rows (device, caller's order) -> columns 0 .. B-1 of a [LTOMPC_NTHETA][Bp] plane (ltompc_set_instance_params_dev)

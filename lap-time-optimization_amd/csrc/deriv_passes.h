@@ -24,11 +24,13 @@ void sens_factorise(ltompc_solver* h) {
   const int N = h->N, Bp = h->Bp;
   const bool ref = h->ref_eval, ell = h->K.bd.nel > 0;
   const auto run = [&](auto eval8, auto eval, auto riccati8, auto* d_W, const auto& W) {
-    if (h->eval8) hipLaunchKernelGGL(eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, d_W);
+    if (h->eval8 && !h->ts_solve) hipLaunchKernelGGL(eval8, dim3(N * (Bp / 8)), dim3(64), 0, h->stream, (const Consts*)h->d_K, d_W);
     else hipLaunchKernelGGL(eval, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, (const Consts*)h->d_K, d_W);
     hipLaunchKernelGGL(riccati8, dim3(Bp / 8), dim3(64), 0, h->stream, h->K, W, (const int*)h->W.si, D.d_sens_inertia);
   };
-  if (h->pi_solve)
+  if (h->ts_solve)  // (with table sets: thread-per-slot as the solve; the head-less sweep reads no table, the _pi one on the WorkPI part)
+    run(k_sens_eval8_pi, ref ? k_sens_eval_ts<BoundsRef> : k_sens_eval_ts<BoundsAny>, k_sens_riccati8_pi, (const WorkTS*)D.d_Wsts, D.Wspi);
+  else if (h->pi_solve)
     run(k_sens_eval8_pi, ref ? k_sens_eval_pi<BoundsRef> : k_sens_eval_pi<BoundsAny>, k_sens_riccati8_pi, (const WorkPI*)D.d_Wspi, D.Wspi);
   else
     run(k_sens_eval8, ell ? (ref ? k_sens_eval<BoundsRef, true> : k_sens_eval<BoundsAny, true>)
@@ -42,7 +44,7 @@ void sens_factorise(ltompc_solver* h) {
 // trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
 int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
   DerivState& D = h->dv;
-  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess and set_table_values discard the last solve)");
+  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess, set_table_values and set_table_sets discard the last solve)");
   const int B = h->B, N = h->N, Bp = h->Bp;
   if (!D.d_Ws) {
     Work& Ws = D.Ws = h->W;
@@ -76,9 +78,17 @@ int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
   return 0;
 }
 
+// The passes that per-instance table sets do not cover: a worded usage error.
+int no_table_sets(ltompc_solver* h, const char* who, const char* what) {
+  if (h->n_sets)
+    return fail(std::string(who) + ": " + what + " not available on a handle with per-instance table sets (ltompc_set_table_sets; n_sets = 0 and a new solve bring it back)");
+  return 0;
+}
+
 // What both passes over theta need: a problem that theta covers, a solve to differentiate whose u_prev was kept, the PV buffers.
 int psens_prepare(ltompc_solver* h, const char* who) {
   DerivState& D = h->dv;
+  if (no_table_sets(h, who, "the derivatives w.r.t. the vehicle and cost parameters are")) return -1;
   if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
   if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
   if (sens_compute(h, false, who)) return -1;  // (the usage error before a solve comes from here)
@@ -155,8 +165,13 @@ int adj_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, co
 // be null), into d_tab_sg and d_tab_gt: the factorisation when not there, the sweep that keeps the adjoint trajectory, the
 // per-slot contraction, then the scatter to the knots into the zeroed d_tab_gt.  It needs no u_prev, so it also runs after a
 // rollout.  Once its buffers exist it only enqueues.
-int tab_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, const char* who) {
+// `sets`: the caller is one of the per-set entry points (grad_sets in d_tab_gs, [n_sets][4][n_table]); each kind of handle has its own.
+int tab_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, const char* who, const bool sets = false) {
   DerivState& D = h->dv;
+  if (!sets && h->n_sets)
+    return fail(std::string(who) + ": this handle has per-instance table sets, its table gradient is one per set: ltompc_get_adjoint_table_sets / ltompc_adjoint_table_sets_dev");
+  if (sets && !h->n_sets)
+    return fail(std::string(who) + ": this handle has no table sets (ltompc_set_table_sets), its table gradient is ltompc_get_adjoint_tables / ltompc_adjoint_tables_dev");
   if (!gX_dev && !gU_dev) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
   if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
   if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
@@ -168,8 +183,26 @@ int tab_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, co
       return -1;
     HIPCHECK(hipStreamSynchronize(h->stream));
   }
+  if (sets && h->n_sets > D.tab_gs_cap) {  // (grows with the number of sets, as the value buffer)
+    double* fresh = nullptr;
+    if (h->dalloc(&fresh, (size_t)TAB_ROWS * h->n_table * h->n_sets)) return -1;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->dfree(D.d_tab_gs);
+    D.d_tab_gs = fresh, D.tab_gs_cap = h->n_sets;
+  }
   sens_factorise(h);
   const dim3 slots((N * Bp + 63) / 64), block(64);
+  const size_t nthreads = (size_t)3 * N * Bp;
+  if (sets) {  // (the sweep reads no table: the _pi one; the contraction on each instance's rows; the scatter into the block of its set)
+    hipLaunchKernelGGL(k_adj_sweep_tab_pi, dim3(Bp / 8), block, 0, h->stream, D.Wspi, gX_dev, gU_dev, D.d_tab_tj);
+    hipLaunchKernelGGL(h->ref_eval ? k_tab_cond_ts<BoundsRef> : k_tab_cond_ts<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
+                       (const WorkTS*)h->d_Wts, (const double*)D.d_tab_tj, (const int*)D.d_sens_ok, D.d_tab_sg);
+    HIPCHECK(hipMemsetAsync(D.d_tab_gs, 0, sizeof(double) * TAB_ROWS * h->n_table * h->n_sets, h->stream));
+    hipLaunchKernelGGL(k_tab_scatter_ts, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, h->stream, (const Consts*)h->d_K, h->W,
+                       (const int*)D.d_sens_ok, (const double*)D.d_tab_sg, D.d_tab_gs, (const int*)h->d_ts_idx);
+    HIPCHECK(hipGetLastError());
+    return 0;
+  }
   if (h->pi_solve) {
     hipLaunchKernelGGL(k_adj_sweep_tab_pi, dim3(Bp / 8), block, 0, h->stream, D.Wspi, gX_dev, gU_dev, D.d_tab_tj);
     hipLaunchKernelGGL(h->ref_eval ? k_tab_cond_pi<BoundsRef> : k_tab_cond_pi<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
@@ -180,7 +213,6 @@ int tab_compute(ltompc_solver* h, const double* gX_dev, const double* gU_dev, co
                        (const Work*)h->d_W, (const double*)D.d_tab_tj, (const int*)D.d_sens_ok, D.d_tab_sg);
   }
   HIPCHECK(hipMemsetAsync(D.d_tab_gt, 0, sizeof(double) * TAB_ROWS * h->n_table, h->stream));
-  const size_t nthreads = (size_t)3 * N * Bp;
   hipLaunchKernelGGL(k_tab_scatter, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, h->stream, (const Consts*)h->d_K, h->W,
                      (const int*)D.d_sens_ok, (const double*)D.d_tab_sg, D.d_tab_gt);
   HIPCHECK(hipGetLastError());
@@ -381,6 +413,57 @@ int ltompc_get_adjoint_tables(ltompc_handle h, const double* gX, const double* g
   return 0;
 }
 
+// The same three calls on a handle with per-instance table sets: grad_sets [n_sets][4][n_table], each set's block
+// summed over the ok instances of that set; slot_grad and ok as above.
+int ltompc_adjoint_table_sets_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_sets_dev, double* slot_grad_dev,
+                                  int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_table_sets_dev", true)) return -1;
+  if (copy_out(h, D2D, grad_sets_dev, h->dv.d_tab_gs, (size_t)TAB_ROWS * h->n_table * h->n_sets)) return -1;
+  if (copy_out(h, D2D, slot_grad_dev, h->dv.d_tab_sg, (size_t)TS_NS * h->N * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_adjoint_table_sets_add_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_sets_dev, double* slot_grad_dev,
+                                      int* ok_dev) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_table_sets_add_dev", true)) return -1;
+  if (grad_sets_dev) {
+    const int n = TAB_ROWS * h->n_table * h->n_sets;
+    hipLaunchKernelGGL(k_tab_add, dim3((n + 255) / 256), dim3(256), 0, h->stream, grad_sets_dev, (const double*)h->dv.d_tab_gs, n);
+    HIPCHECK(hipGetLastError());
+  }
+  if (copy_out(h, D2D, slot_grad_dev, h->dv.d_tab_sg, (size_t)TS_NS * h->N * h->B)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_adjoint_table_sets(ltompc_handle h, const double* gX, const double* gU, double* grad_sets, double* slot_grad, int* ok) {
+  const char* who = "ltompc_get_adjoint_table_sets";
+  if (!h) return fail("null handle");
+  if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
+  const size_t B = h->B, N = h->N;
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; gX && e < (N + 1) * 8; e++) fin = fin && std::isfinite(gX[b * (N + 1) * 8 + e]);
+    for (size_t e = 0; gU && e < N * 2; e++) fin = fin && std::isfinite(gU[b * N * 2 + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite cotangent of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  DerivState& D = h->dv;
+  if (gX && !D.d_adj_gX && h->dalloc(&D.d_adj_gX, (N + 1) * 8 * B)) return -1;
+  if (gU && !D.d_adj_gU && h->dalloc(&D.d_adj_gU, N * 2 * B)) return -1;
+  if (gX) HIPCHECK(hipMemcpyAsync(D.d_adj_gX, gX, sizeof(double) * (N + 1) * 8 * B, hipMemcpyHostToDevice, h->stream));
+  if (gU) HIPCHECK(hipMemcpyAsync(D.d_adj_gU, gU, sizeof(double) * N * 2 * B, hipMemcpyHostToDevice, h->stream));
+  if (tab_compute(h, gX ? D.d_adj_gX : nullptr, gU ? D.d_adj_gU : nullptr, who, true)) return -1;
+  if (copy_out(h, D2H, grad_sets, D.d_tab_gs, (size_t)TAB_ROWS * h->n_table * h->n_sets) || copy_out(h, D2H, slot_grad, D.d_tab_sg, TS_NS * N * B) ||
+      copy_out(h, D2H, ok, D.d_sens_ok, B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_dev, double* tX_dev, double* tU_dev, int* ok_dev) {
   if (!h) return fail("null handle");
   HIPCHECK(hipSetDevice(h->device));
@@ -420,6 +503,7 @@ int ltompc_plant_sensitivities_dev(ltompc_handle h, const double* x_dev, const d
   if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
   if (!h || !x_dev || !u_dev) return fail(std::string(who) + ": null argument");
   if (dxn_dtheta_dev && h->K.p.ptv != 0.0) return fail(std::string(who) + ": dxn_dtheta is not available with torque vectoring (ptv != 0)");
+  if (no_table_sets(h, who, "the plant-step sensitivities are")) return -1;
   HIPCHECK(hipSetDevice(h->device));
   if (psn_prepare(h, false)) return -1;
   if (dxn_dx_dev || dxn_du_dev || dxn_dtheta_dev) {
@@ -438,6 +522,7 @@ int ltompc_plant_sensitivities(ltompc_handle h, const double* x, const double* u
   const char* who = "ltompc_plant_sensitivities";
   if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
   if (!h || !x || !u) return fail(std::string(who) + ": null argument");
+  if (no_table_sets(h, who, "the plant-step sensitivities are")) return -1;
   HIPCHECK(hipSetDevice(h->device));
   if (psn_prepare(h, false)) return -1;
   const size_t B = h->B;
@@ -452,6 +537,7 @@ int ltompc_loop_begin(ltompc_handle h, int mode) {
   const char* who = "ltompc_loop_begin";
   if (!h) return fail("null handle");
   if (mode < 1 || mode > 3) return fail(std::string(who) + ": mode must be 1 (theta enters the controller), 2 (the plant) or 3 (both)");
+  if (no_table_sets(h, who, "the closed-loop sensitivities are")) return -1;
   if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
   if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
   HIPCHECK(hipSetDevice(h->device));
@@ -470,6 +556,7 @@ int ltompc_loop_tick_dev(ltompc_handle h, const double* x_dev, const double* u0_
   if (!h || !x_dev || !u0_dev || !x_next_dev) return fail(std::string(who) + ": null argument");
   DerivState& D = h->dv;
   if (!D.loop_mode) return fail(std::string(who) + ": no loop (ltompc_loop_begin first)");
+  if (no_table_sets(h, who, "the closed-loop sensitivities are")) return -1;
   HIPCHECK(hipSetDevice(h->device));
   if (sens_compute(h, false, who)) return -1;  // (the usage error after set_initial_guess comes from here)
   if (!D.kept_uprev) return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, which the r_du columns need)");

@@ -43,6 +43,12 @@
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
+//   *_ts          the kernels above that read a value row of the track tables, a third time with per-instance table sets
+//                 (ltompc_set_table_sets): the same device functions instantiated with PI = true and TS = true,
+//                 K.T replaced by inst_tables<TS>(K.T, W, b) - the handle's tables with the four value pointers moved to the
+//                 rows of the instance's set, read through WorkTS (layout.h).  Thread-per-slot evaluation only; the Riccati
+//                 heads and d_pick are among them (lterm(x_0) reads v_ref when the smoothing changes); the sweeps of the
+//                 derivative passes read no table and stay the _pi ones; the uniform and _pi kernels are unchanged
 #pragma once
 #include "layout.h"
 #include "linearise.h"

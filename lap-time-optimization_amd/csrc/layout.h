@@ -145,6 +145,40 @@ __device__ __forceinline__ double inst_r_du(const ltompc_params& u, const Work& 
   else return u.r_du[i];
 }
 
+// Work of the _ts kernels (per-instance track table sets, ltompc_set_table_sets): WorkPI with two fields appended,
+// TSV, the value rows of the sets, [n_sets][LTOMPC_TABLE_VALUE_ROWS][n_table], and TSI, the set of every instance, [Bp] in the
+// CALLER's instance order (indexed by orig[b], as TH and BK; every entry in [0, n_sets), pad entries 0).  A struct of its own
+// for the reason given for WorkPI; the _ts family is PI and TS together, so a WorkTS is a WorkPI with TH filled.
+struct WorkTS : WorkPI {
+  gptr<const double> TSV;
+  gptr<const int> TSI;
+};
+
+// The tables with the four value rows of set `set` of `tsv` (grids, g0_*, inv_* and period are the handle's).
+template <class P>
+__device__ __forceinline__ Tables set_tables(const Tables& u, const P tsv, const int set) {
+  Tables t = u;
+  const size_t n = (size_t)u.n;
+  const auto v = (gptr<const double>)(tsv + (size_t)set * (LTOMPC_TABLE_VALUE_ROWS * n));  // (tsv may be a plain pointer: a kernel argument)
+  t.kappa = v, t.n_left = v + n, t.n_right = v + 2 * n, t.v_ref = v + 3 * n;
+  return t;
+}
+// TS = false: the handle's tables themselves (the existing kernels, unchanged); TS = true: those of set `set` of tsv
+template <bool TS, class P>
+__device__ __forceinline__ decltype(auto) sel_tables(const Tables& u, const P tsv, const int set) {
+  if constexpr (TS) return set_tables(u, tsv, set);
+  else return (u);
+}
+// ... of the set of the instance in
+// slot b.  Called with TS = true by the _ts kernels only, whose Work IS a WorkTS.
+template <bool TS>
+__device__ __forceinline__ decltype(auto) inst_tables(const Tables& u, const Work& W, const int b) {
+  if constexpr (TS) {
+    const WorkTS& Wt = static_cast<const WorkTS&>(W);
+    return set_tables(u, Wt.TSV, Wt.TSI[W.orig[b]]);
+  } else return (u);
+}
+
 // What changes from launch to launch (kernel argument; Work and Consts are read from device memory).  Compaction of the
 // unfinished instances: thread j of a launch works on instance act[j], j < nact[0] <= the launch width.  The list is
 // sorted (stable compaction), so while nothing has finished it is the identity and accesses coalesce.

@@ -86,7 +86,7 @@ __device__ __forceinline__ void track_soft_step(const double rho, const double m
 
 // Slacks, inequality multipliers (and elastic variables) of slot k from its primal point (k_init at the start of a
 // solve, reinit_slot when the restoration phase is entered): t = max(-h, bound_push), nu = mu / t.
-template <class BP>
+template <class BP, bool TS = false>
 __device__ __forceinline__ void init_slot_slacks(const Consts& K, const Work& W, const int k, const int b, const double mu,
                                                  const double eps, const double rho, const double* xp, const double* c,
                                                  const double* u) {
@@ -98,7 +98,7 @@ __device__ __forceinline__ void init_slot_slacks(const Consts& K, const Work& W,
     PL(W.T, mm, k, N) = t, PL(W.NU, mm, k, N) = mu / t;
   });
   double gv[3] = {-1.0, -1.0, -1.0};
-  if (k + 1 <= N - 1) cons_eval(K.p, K.T, eps, xp, gv, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (k + 1 <= N - 1) cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, xp, gv, nullptr, nullptr, nullptr, nullptr, nullptr);
 #pragma unroll
   for (int q = 0; q < 3; q++) {
     double t = -gv[q] > K.o.bound_push ? -gv[q] : K.o.bound_push, e = 0.0;
@@ -139,7 +139,7 @@ __device__ __forceinline__ void init_slot_slacks(const Consts& K, const Work& W,
 // primal point with the instance's new barrier parameter and penalty, the collocation multipliers at zero.  Everything
 // written here belongs to slot k alone (the one neighbour's access, L1 / L2 of slot k + 1 in the dual residual of d_eval,
 // is replaced by zeros while the flag is set).
-template <class BP>
+template <class BP, bool TS = false>
 __device__ __forceinline__ void reinit_slot(const Consts& K, const Work& W, const int k, const int b) {
   const int N = W.N;
   const double mu = W.st[(size_t)ST_MU * W.Bp + b], eps = W.st[(size_t)ST_EPS * W.Bp + b], rho = W.st[(size_t)ST_RHO * W.Bp + b];
@@ -147,7 +147,7 @@ __device__ __forceinline__ void reinit_slot(const Consts& K, const Work& W, cons
 #pragma unroll
   for (int i = 0; i < 8; i++) xp[i] = PL(W.X, i, k + 1, N + 1), c[i] = PL(W.C, i, k, N);
   u[0] = PL(W.U, 0, k, N), u[1] = PL(W.U, 1, k, N);
-  init_slot_slacks<BP>(K, W, k, b, mu, eps, rho, xp, c, u);
+  init_slot_slacks<BP, TS>(K, W, k, b, mu, eps, rho, xp, c, u);
 #pragma unroll
   for (int i = 0; i < 8; i++) PL(W.L1, i, k, N) = 0.0, PL(W.L2, i, k, N) = 0.0;
 }
@@ -174,7 +174,7 @@ struct Slot {
   bool nl;
 };
 
-template <bool WITH_DUAL, class BP, bool ELL, bool PI = false>
+template <bool WITH_DUAL, class BP, bool ELL, bool PI = false, bool TS = false>
 __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, int k, int b, double eps, Slot& S) {
   const int N = W.N;
   const double hdt = K.o.t_step, rho = W.st[(size_t)ST_RHO * W.Bp + b];
@@ -191,12 +191,12 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
 #pragma unroll
   for (int i = 0; i < 36; i++) S.Hc[i] = 0.0, S.Hxp[i] = 0.0;
   double f1[8], f2[8], J[48];
-  rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, S.c, f1, J, l1, hdt, S.Hc);
+  rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.c, f1, J, l1, hdt, S.Hc);
 #pragma unroll
   for (int i = 0; i < 64; i++) S.E1[i] = 0.0, S.E2[i] = 0.0;
 #pragma unroll
   for (int i = 0; i < 48; i++) S.E1[i] = hdt * J[i];
-  rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, f2, J, l2, hdt, S.Hxp);
+  rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.xp, f2, J, l2, hdt, S.Hxp);
 #pragma unroll
   for (int i = 0; i < 48; i++) S.E2[i] = hdt * J[i];
   f1[6] = f2[6] = S.u[0], f1[7] = f2[7] = S.u[1];
@@ -208,7 +208,7 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
   }
 #pragma unroll
   for (int i = 0; i < 8; i++) S.gcost[i] = 0.0, S.gc0[i] = 0.0, S.gc1[i] = 0.0, S.gxp1[i] = 0.0, S.dcd[i] = 0.0;
-  S.cost = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, S.xp, k == N - 1, S.gcost, S.Hxp);
+  S.cost = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.xp, k == N - 1, S.gcost, S.Hxp);
 #pragma unroll
   for (int i = 0; i < 8; i++) S.gxp0[i] = S.gcost[i], S.dxd[i] = S.gcost[i];
   S.Du[0] = S.Du[1] = 0.0, S.gub0[0] = S.gub0[1] = 0.0, S.gub1[0] = S.gub1[1] = 0.0, S.dud[0] = S.dud[1] = 0.0;
@@ -253,7 +253,7 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
     asm volatile("" : "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(nq[0]), "+v"(nq[1]), "+v"(nq[2]), "+v"(eq[0]), "+v"(eq[1]), "+v"(eq[2]));
 #endif
     double hss[3], hmm[3];
-    cons_eval(K.p, K.T, eps, S.xp, S.gv, S.gs, S.gn, S.gm, hss, hmm);
+    cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, S.xp, S.gv, S.gs, S.gn, S.gm, hss, hmm);
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       int mm = m_nl + q;
@@ -476,7 +476,7 @@ __device__ __forceinline__ bool condense_slot(const Consts& K, const Slot& S, M8
 
 
 // ------------------------------------------------------------------------------------------ k_eval
-template <class BP, bool ELL, bool PI = false>
+template <class BP, bool ELL, bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_eval(const Consts& K, const Work& W, const int k, const int b, const bool force) {
   const int N = W.N;
   if (W.si[(size_t)SI_DONE * W.Bp + b]) return;
@@ -484,9 +484,9 @@ __device__ __forceinline__ void d_eval(const Consts& K, const Work& W, const int
   const double hdt = K.o.t_step;
   const double eps = W.st[(size_t)ST_EPS * W.Bp + b];
   const bool reinit = W.si[(size_t)SI_REINIT * W.Bp + b] != 0;  // the restoration phase starts with this evaluation
-  if (reinit) reinit_slot<BP>(K, W, k, b);
+  if (reinit) reinit_slot<BP, TS>(K, W, k, b);
   Slot S;
-  linearise_slot<true, BP, ELL, PI>(K, W, k, b, eps, S);
+  linearise_slot<true, BP, ELL, PI, TS>(K, W, k, b, eps, S);
   // ---- node block of x_{k+1}: complete after the linearisation, stored now so that its 52 registers are free during
   //      the elimination (stores issued late also cost more than their bandwidth: on gfx9 a later scratch reload
   //      has to wait for every store before it, vmcnt counts both)
@@ -603,10 +603,20 @@ __global__ void __launch_bounds__(64) k_eval_pi(const Consts* __restrict__ Kp, c
   if (k >= W.N || j >= la.nact[0]) return;
   d_eval<BP, false, true>(K, W, k, la.act[j], la.force_eval != 0);
 }
+// ... and per-instance table sets (W.TSV / W.TSI)
+template <class BP>
+__global__ void __launch_bounds__(64) k_eval_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = tid % la.n_pad, k = tid / la.n_pad;
+  if (k >= W.N || j >= la.nact[0]) return;
+  d_eval<BP, false, true, true>(K, W, k, la.act[j], la.force_eval != 0);
+}
 
 
 // ------------------------------------------------------------------------------------------ k_expand
-template <class BP, bool ELL, bool PI = false>
+template <class BP, bool ELL, bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_expand(const Consts& K, const Work& W, const int k, const int b) {
   const int N = W.N;
   if (W.si[(size_t)SI_DONE * W.Bp + b] || !W.si[(size_t)SI_STEP * W.Bp + b]) return;  // no step this launch
@@ -642,7 +652,7 @@ __device__ __forceinline__ void d_expand(const Consts& K, const Work& W, const i
   //  above the costate, runs out of registers and spills the Riccati words one by one, each spill waiting for its load)
   __builtin_amdgcn_sched_barrier(0);
   Slot S;
-  linearise_slot<false, BP, ELL, PI>(K, W, k, b, eps, S);
+  linearise_slot<false, BP, ELL, PI, TS>(K, W, k, b, eps, S);
   M8Blocks M8;
   factor_m8(S, M8);
   double dxk[8], dxp[8], du[2], dc[8];
@@ -797,6 +807,16 @@ __global__ void __launch_bounds__(64) k_expand_pi(const Consts* __restrict__ Kp,
   int j = tid % la.n_pad, k = tid / la.n_pad;
   if (k >= W.N || j >= la.nact[0]) return;
   d_expand<BP, false, true>(K, W, k, la.act[j]);
+}
+// ... and per-instance table sets (W.TSV / W.TSI)
+template <class BP>
+__global__ void __launch_bounds__(64) k_expand_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = tid % la.n_pad, k = tid / la.n_pad;
+  if (k >= W.N || j >= la.nact[0]) return;
+  d_expand<BP, false, true, true>(K, W, k, la.act[j]);
 }
 
 }  // namespace ltompc

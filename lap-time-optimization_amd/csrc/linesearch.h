@@ -12,7 +12,7 @@ namespace ltompc {
 // for every instance; phase 1 evaluates the remaining candidates for the instances whose first candidate was rejected.
 // Filter measures (theta, cost, sum log t) of the step candidates l_begin..l_end of interval k of instance b;
 // candidate l >= 1 has alpha = a_pri * 2^-(l-1) (l = 0, the current point, is written by k_eval).
-template <class BP, bool PIN, bool ELL, bool PI = false>
+template <class BP, bool PIN, bool ELL, bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, const int k, const int b, const int l_begin,
                                              const int l_end) {
   const int N = W.N;
@@ -51,15 +51,15 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
 #pragma unroll
     for (int i = 0; i < 2; i++) tu[i] = u[i] + alpha * du[i], tv[i] = v[i] + alpha * dv[i];
     double f1[8], f2[8];
-    rhs_val(inst_params<PI>(K.p, W, b), K.T, eps, tc, tu, f1);
-    rhs_val(inst_params<PI>(K.p, W, b), K.T, eps, txp, tu, f2);
+    rhs_val(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, tc, tu, f1);
+    rhs_val(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, txp, tu, f2);
     double th = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       th += fabs(hdt * f1[i] + 2.0 * txk[i] - 1.5 * tc[i] - 0.5 * txp[i]);
       th += fabs(hdt * f2[i] - 2.0 * txk[i] + 4.5 * tc[i] - 2.5 * txp[i]);
     }
-    double co = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, txp, k == N - 1, nullptr, nullptr);
+    double co = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, txp, k == N - 1, nullptr, nullptr);
 #pragma unroll
     for (int i = 0; i < 2; i++) co += inst_r_du<PI>(K.p, W, b, i) * (tu[i] - tv[i]) * (tu[i] - tv[i]);
     // sum of log t as the log of products of 8 slacks (same grouping in linearise_slot): 3 logarithms instead of 23
@@ -91,7 +91,7 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
     });
     if (nl) {
       double gv[3];
-      cons_eval(K.p, K.T, eps, txp, gv, nullptr, nullptr, nullptr, nullptr, nullptr);
+      cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, txp, gv, nullptr, nullptr, nullptr, nullptr, nullptr);
 #pragma unroll
       for (int q = 0; q < 3; q++) {
         double t = PL(W.T, m + q, k, N) + alpha * PL(W.dT, m + q, k, N);
@@ -155,13 +155,30 @@ __global__ void __launch_bounds__(64) k_linesearch_pi(const Consts* __restrict__
   for (int j = j0; j < count; j += jw) d_linesearch<BP, true, false, true>(K, W, k, phase == 0 ? la.act[j] : W.ls_list[j], l, l);
 }
 
+// ... and per-instance table sets (W.TSV / W.TSI)
+template <class BP>
+__global__ void __launch_bounds__(64) k_linesearch_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la, int phase, int jw) {
+  const Consts& K = *Kp;  // K and W live in device memory: fields are fetched where they are used instead of
+  const Work& W = *Wp;    // occupying (spilled) SGPRs for the whole kernel
+  // phase 0: thread = (k, j), evaluates the first candidate (full step to the boundary) of instance act[j].
+  // phase 1: thread = (candidate, k, j'), one candidate each (latency matters here, not throughput), over the packed
+  //          list of rejected instances; jw = launch width in instances, longer lists are covered grid-stride.
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = W.N;
+  const int j0 = tid % jw, rest = tid / jw, k = rest % N, cand = rest / N;
+  if (phase == 0 ? (rest >= N) : (cand >= K.o.n_linesearch - 1)) return;
+  const int count = phase == 0 ? la.nact[0] : W.ls_count[0];
+  const int l = phase == 0 ? 1 : 2 + cand;
+  for (int j = j0; j < count; j += jw) d_linesearch<BP, true, false, true, true>(K, W, k, phase == 0 ? la.act[j] : W.ls_list[j], l, l);
+}
+
 // ------------------------------------------------------------------------------------------ k_pick
 // Filter line search of Waechter & Biegler 2006 (no second-order correction, no restoration phase).
 // 8 lanes per instance (lane = g + 8 i, all 8 lanes of a group call this together): lane i reduces the stage partials
 // k = i, i+8, ...; the 8 lanes then hold the same numbers and take the same decisions, lane i == 0 writes.  (Keeps the
 // latency of this small step at N/8 dependent loads instead of N.)
 constexpr int PICK_Q = 5;  // stages per lane and round trip: N = 40 in one (with 8, k_step1's 256 registers do not hold the batch)
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int b, const int i, const int phase,
                                        const bool append_list) {
   const int N = W.N;
@@ -375,7 +392,7 @@ __device__ __forceinline__ void d_pick(const Consts& K, const Work& W, const int
   // table smoothing follows the barrier parameter with one iteration lag; the filter restarts when it changes
   const bool eps_switched = eps_next != eps;
   if (eps_switched) {
-    c00 = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps_next, x0, false, nullptr, nullptr);
+    c00 = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps_next, x0, false, nullptr, nullptr);
     nfilt = 0, th_reset = true;
   }
   // ---- the stores, in one group
@@ -429,6 +446,17 @@ __global__ void __launch_bounds__(64) k_pick_pi(const Consts* __restrict__ Kp, c
   // (phase 1 is launched for the expected length of the list of rejected steps, longer lists are covered grid-stride;
   //  the 8 lanes of an instance stay together)
   for (int j = blockIdx.x * 8 + g; j < count; j += gridDim.x * 8) d_pick<true>(K, W, phase == 0 ? la.act[j] : W.ls_list[j], i, phase, true);
+}
+
+// ... and per-instance table sets (W.TSV / W.TSI, DESIGN.md §16: d_pick evaluates lterm(x_0) when the smoothing changes)
+__global__ void __launch_bounds__(64) k_pick_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la, int phase) {
+  const Consts& K = *Kp;  // K and W live in device memory: fields are fetched where they are used instead of
+  const Work& W = *Wp;    // occupying (spilled) SGPRs for the whole kernel
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int count = phase == 0 ? la.nact[0] : W.ls_count[0];
+  // (phase 1 is launched for the expected length of the list of rejected steps, longer lists are covered grid-stride;
+  //  the 8 lanes of an instance stay together)
+  for (int j = blockIdx.x * 8 + g; j < count; j += gridDim.x * 8) d_pick<true, true>(K, W, phase == 0 ? la.act[j] : W.ls_list[j], i, phase, true);
 }
 
 // ------------------------------------------------------------------------------------------ k_update
@@ -578,6 +606,38 @@ __global__ void __launch_bounds__(320) k_step1_pi(const Consts* __restrict__ Kp,
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK
 }
+// ... and per-instance table sets (W.TSV / W.TSI): once more the body of k_step1, with the _ts device functions
+// (tests/test_table_sets_resources.py checks the text).
+template <class BP>
+__global__ void __launch_bounds__(320) k_step1_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la) {  // 320 = 8 candidates x 40 intervals in one pass
+  const Consts& K = *Kp;  // K and W live in device memory: fields are fetched where they are used instead of
+  const Work& W = *Wp;    // occupying (spilled) SGPRs for the whole kernel
+  if ((int)blockIdx.x >= la.nact[0]) return;
+  const int b = la.act[blockIdx.x];
+  const int N = W.N, tid = threadIdx.x;
+  const int* si = W.si;
+  if (si[(size_t)SI_DONE * W.Bp + b] || !si[(size_t)SI_STEP * W.Bp + b]) return;  // block-uniform
+  // all step candidates at once (the threads are there anyway; the wide path evaluates candidates 2.. only for the
+  // instances that rejected the full step, with the same arithmetic)
+  // LTOMPC_DBG: shader-clock cycles of block 0 per section (own line search, all line searches, pick, update), slots 8..12
+  const bool rprof = W.DBG != nullptr && blockIdx.x == 0 && tid == 0;
+  long long rt0 = rprof ? clock64() : 0;
+#define STOCK(q) if (rprof) { const long long t1 = clock64(); W.DBG[q] += (double)(t1 - rt0); rt0 = t1; }
+  for (int idx = tid; idx < N * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, false, true, true>(K, W, idx % N, b, 1 + idx / N, 1 + idx / N);
+  STOCK(8);
+  __syncthreads();
+  STOCK(9);
+  // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
+  //  measures of all candidates exist already: one pass, same decisions)
+  if (tid < 64 && (tid & 7) == 0) d_pick<true, true>(K, W, b, tid >> 3, 1, false);
+  __syncthreads();
+  STOCK(10);
+  for (int kk = tid; kk < N; kk += 320) d_update(K, W, kk, b);
+  STOCK(11);
+  if (rprof) W.DBG[12] += 1.0;
+#undef STOCK
+}
+
 
 
 }  // namespace ltompc

@@ -71,6 +71,10 @@ struct DerivState {
   int *d_loop_ok = nullptr, *d_loop_ticks = nullptr;
   // table-gradient pass (table_sensitivity.h): the adjoint trajectory planes, slot_grad (B x N x 10) and grad_tables (4 x n_table)
   double *d_tab_tj = nullptr, *d_tab_sg = nullptr, *d_tab_gt = nullptr;
+  // ... with table sets: Wsts = Wspi with the set buffers, grad_sets (tab_gs_cap sets x 4 x n_table)
+  WorkTS Wsts{}, *d_Wsts = nullptr;
+  double* d_tab_gs = nullptr;
+  int tab_gs_cap = 0;
 };
 
 struct ltompc_solver {
@@ -149,6 +153,20 @@ struct ltompc_solver {
   bool pi_narrow = true;  // the narrow _pi Riccati kernels got their LDS limit (else the _pi path runs k_riccati8_pi at every width: same bits)
   WorkPI Wpi{};  // W with TH = d_th_solve (layout.h), and its device copy: the _pi kernels' Work (dv.Wspi: the same of dv.Ws)
   WorkPI* d_Wpi = nullptr;
+  // per-instance track table sets (ltompc_set_table_sets).  n_sets > 0: sets are in effect from the next solve,
+  // plant step and rollout on (a set discards the last solve's derivatives, so the passes never see sets other than the solve's).
+  // d_ts_vals [ts_cap][4][n_table], d_ts_idx [Bp] (caller's order, every entry in [0, n_sets), pads 0): one buffer each, no
+  // pending / solved pair.  d_th_unif: a [LTOMPC_NTHETA][Bp] plane of the handle's own params, the rows of a solve with sets but
+  // without theta rows (the _ts family is PI and TS together).  Wts = Wpi with the two buffers; nothing of this exists on a
+  // handle that never had sets.
+  int n_sets = 0, ts_cap = 0;
+  int ts_idx_sets = 1;  // the n_sets the index in effect was written for (1: the zeros it starts with)
+  double *d_ts_vals = nullptr, *d_th_unif = nullptr;
+  int* d_ts_idx = nullptr;
+  bool ts_solve = false;   // the last solve ran the _ts kernels
+  bool ts_narrow = true;   // the narrow _ts Riccati kernels got their LDS limit (as pi_narrow)
+  WorkTS Wts{};
+  WorkTS* d_Wts = nullptr;
 
   // (P may be a gptr<T>: a global-address-space pointer in the device pass of the compiler, a plain one on the host)
   // work = true: an array that the kernels fill before they read it.  LTOMPC_POISON=1 (debug) fills those with 0xFF bytes
@@ -166,6 +184,13 @@ struct ltompc_solver {
     allocs.push_back(q);
     *p = (P)q;
     return 0;
+  }
+  // ... and back, for the one kind of buffer that is re-allocated on a live handle (the set values when n_sets grows); the
+  // caller has drained the stream
+  void dfree(void* q) {
+    if (!q) return;
+    allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end());
+    (void)hipFree(q);
   }
 };
 
@@ -223,8 +248,9 @@ struct Launcher {
 // The kernels of an interior-point iteration: the uniform ones, or the _pi ones (per-instance vehicle and cost parameters,
 // DESIGN.md §10) with the WorkPI copies of W.  One launch sequence for both (launch_iteration).  The _pi kernels exist without
 // the friction ellipse only (ltompc_set_instance_params refuses it): their ELL selectors take no `ell`.
-template <bool PI> struct IterKernels;
-template <> struct IterKernels<false> {
+// Family 2, _ts: per-instance table sets on top of the rows, with the WorkTS copies; thread-per-slot evaluation only.
+template <int FAM> struct IterKernels;
+template <> struct IterKernels<0> {
   static const Work* dev(const ltompc_solver* h) { return h->d_W; }
   static const Work& val(const ltompc_solver* h) { return h->W; }
   static int ric1_width(const ltompc_solver* h) { return h->ric1_width; }
@@ -247,7 +273,7 @@ template <> struct IterKernels<false> {
   static auto riccati1() { return k_riccati1; }
   static auto riccati1q() { return k_riccati1q; }
 };
-template <> struct IterKernels<true> {
+template <> struct IterKernels<1> {
   static const WorkPI* dev(const ltompc_solver* h) { return h->d_Wpi; }
   static const WorkPI& val(const ltompc_solver* h) { return h->Wpi; }
   static int ric1_width(const ltompc_solver* h) { return h->pi_narrow ? h->ric1_width : 0; }
@@ -262,17 +288,32 @@ template <> struct IterKernels<true> {
   static auto riccati1() { return k_riccati1_pi; }
   static auto riccati1q() { return k_riccati1q_pi; }
 };
+template <> struct IterKernels<2> {
+  static const WorkTS* dev(const ltompc_solver* h) { return h->d_Wts; }
+  static const WorkTS& val(const ltompc_solver* h) { return h->Wts; }
+  static int ric1_width(const ltompc_solver* h) { return h->ts_narrow ? h->ric1_width : 0; }
+  static auto eval(const ltompc_solver* h, bool) { return h->ref_eval ? k_eval_ts<BoundsRef> : k_eval_ts<BoundsAny>; }
+  static auto expand(const ltompc_solver* h, bool) { return h->ref_expand ? k_expand_ts<BoundsRef> : k_expand_ts<BoundsAny>; }
+  static auto step1(const ltompc_solver* h, bool) { return h->ref_step1 ? k_step1_ts<BoundsRef> : k_step1_ts<BoundsAny>; }
+  static auto linesearch(const ltompc_solver* h, bool) { return h->ref_ls ? k_linesearch_ts<BoundsRef> : k_linesearch_ts<BoundsAny>; }
+  static auto pick() { return k_pick_ts; }
+  static auto riccati8() { return k_riccati8_ts; }
+  static auto riccati1() { return k_riccati1_ts; }
+  static auto riccati1q() { return k_riccati1q_ts; }
+};
 
 // The kernels of one interior-point iteration over the instances of `la` (make_step and the closed-loop rollout share it).
-template <bool PI>
+template <int FAM>
 int launch_iteration_t(ltompc_solver* h, Launcher& L, const Launch& la, const int it, const int n_launch, const int ls_width, const bool ell,
                        const bool riccati_only) {
-  using KS = IterKernels<PI>;
+  using KS = IterKernels<FAM>;
   const int N = h->N, np = la.n_pad;
   const auto* Wd = KS::dev(h);
   const auto& Wv = KS::val(h);
-    if (h->eval8 ? L.run(0, KS::eval8(), N * np * 8, h->d_K, Wd, la) : L.run(0, KS::eval(h, ell), N * np, h->d_K, Wd, la)) return -1;
-    if (!PI && h->serial_riccati) {  // (the _pi path never gets here: a handle with LTOMPC_RICCATI=serial refuses rows)
+    if constexpr (FAM == 2) {  // (handles with sets: the thread-per-slot kernels whatever latency_mode says, as with the friction ellipse)
+      if (L.run(0, KS::eval(h, ell), N * np, h->d_K, Wd, la)) return -1;
+    } else if (h->eval8 ? L.run(0, KS::eval8(), N * np * 8, h->d_K, Wd, la) : L.run(0, KS::eval(h, ell), N * np, h->d_K, Wd, la)) return -1;
+    if (FAM == 0 && h->serial_riccati) {  // (the _pi path never gets here: a handle with LTOMPC_RICCATI=serial refuses rows)
       if (L.run(1, k_riccati, np, h->d_K, h->d_W, la, it)) return -1;
     } else {
       // measured: letting the stragglers retry inside a launch (max_sweeps 4 when n_launch <= 256) finishes them in
@@ -289,7 +330,9 @@ int launch_iteration_t(ltompc_solver* h, Launcher& L, const Launch& la, const in
       } else if (L.run(1, KS::riccati8(), np * 8, h->K, Wv, la, it, max_sweeps)) return -1;  // 8 lanes per instance
     }
     if (riccati_only) return 0;  // (make_step's last pass: only finalises the statuses, MAX_ITER)
-    if (h->eval8 ? L.run(2, KS::expand8(), N * np * 8, h->d_K, Wd, la) : L.run(2, KS::expand(h, ell), N * np, h->d_K, Wd, la)) return -1;
+    if constexpr (FAM == 2) {
+      if (L.run(2, KS::expand(h, ell), N * np, h->d_K, Wd, la)) return -1;
+    } else if (h->eval8 ? L.run(2, KS::expand8(), N * np * 8, h->d_K, Wd, la) : L.run(2, KS::expand(h, ell), N * np, h->d_K, Wd, la)) return -1;
     if (n_launch <= h->step1_width) {
       // one workgroup per instance does both line-search phases, the filter test and the update
       L.block_threads = 320;
@@ -309,8 +352,9 @@ int launch_iteration_t(ltompc_solver* h, Launcher& L, const Launch& la, const in
 }
 int launch_iteration(ltompc_solver* h, Launcher& L, const Launch& la, const int it, const int n_launch, const int ls_width, const bool ell,
                      const bool riccati_only) {
-  return h->pi_solve ? launch_iteration_t<true>(h, L, la, it, n_launch, ls_width, ell, riccati_only)
-                     : launch_iteration_t<false>(h, L, la, it, n_launch, ls_width, ell, riccati_only);
+  return h->ts_solve ? launch_iteration_t<2>(h, L, la, it, n_launch, ls_width, ell, riccati_only)
+         : h->pi_solve ? launch_iteration_t<1>(h, L, la, it, n_launch, ls_width, ell, riccati_only)
+                       : launch_iteration_t<0>(h, L, la, it, n_launch, ls_width, ell, riccati_only);
 }
 
 int collect_profile(ltompc_solver* h) {
@@ -379,6 +423,14 @@ int sync_pi_work(ltompc_solver* h) {
     static_cast<Work&>(h->dv.Wspi) = h->dv.Ws, h->dv.Wspi.TH = (gptr<const double>)h->d_th_solve;
     HIPCHECK(hipMemcpyAsync(h->dv.d_Wspi, &h->dv.Wspi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream));
   }
+  if (h->d_Wts) {  // (a WorkTS is a WorkPI: the same copies once more, with the set buffers)
+    static_cast<WorkPI&>(h->Wts) = h->Wpi, h->Wts.TSV = (gptr<const double>)h->d_ts_vals, h->Wts.TSI = (gptr<const int>)h->d_ts_idx;
+    HIPCHECK(hipMemcpyAsync(h->d_Wts, &h->Wts, sizeof(WorkTS), hipMemcpyHostToDevice, h->stream));
+    if (h->dv.d_Ws) {
+      static_cast<WorkPI&>(h->dv.Wsts) = h->dv.Wspi, h->dv.Wsts.TSV = h->Wts.TSV, h->dv.Wsts.TSI = h->Wts.TSI;
+      HIPCHECK(hipMemcpyAsync(h->dv.d_Wsts, &h->dv.Wsts, sizeof(WorkTS), hipMemcpyHostToDevice, h->stream));
+    }
+  }
   HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -413,8 +465,46 @@ int theta_prepare(ltompc_solver* h, const char* who) {
 int commit_theta(ltompc_solver* h) {
   if (h->pi_pend)
     HIPCHECK(hipMemcpyAsync(h->d_th_solve, h->d_th_pend, sizeof(double) * LTOMPC_NTHETA * h->Bp, hipMemcpyDeviceToDevice, h->stream));
-  h->pi_solve = h->pi_pend;
+  else if (h->n_sets)  // (sets without rows: the _ts kernels read every instance's params from TH, here the handle's own)
+    HIPCHECK(hipMemcpyAsync(h->d_th_solve, h->d_th_unif, sizeof(double) * LTOMPC_NTHETA * h->Bp, hipMemcpyDeviceToDevice, h->stream));
+  h->ts_solve = h->n_sets > 0;
+  h->pi_solve = h->pi_pend || h->ts_solve;
   return 0;
+}
+
+// Table sets: the checks every set makes (those of the rows: the _ts family is PI and TS together) and, on the first, the index,
+// the plane of the handle's own params, the WorkTS copies and the LDS limit of the narrow _ts Riccati kernels.
+int ts_prepare(ltompc_solver* h, const char* who) {
+  if (theta_prepare(h, who)) return -1;
+  if (h->d_ts_idx) return 0;
+  const size_t Bp = h->Bp;
+  std::vector<double> plane((size_t)LTOMPC_NTHETA * Bp);
+  double t[LTOMPC_NTHETA];
+  theta_of(h->K.p, t);
+  for (int j = 0; j < LTOMPC_NTHETA; j++)
+    for (size_t b = 0; b < Bp; b++) plane[j * Bp + b] = t[j];
+  if (h->dalloc(&h->d_th_unif, plane.size()) || h->dalloc(&h->d_ts_idx, Bp) || h->dalloc(&h->d_Wts, 1) || h->dalloc(&h->dv.d_Wsts, 1)) return -1;
+  HIPCHECK(hipMemcpyAsync(h->d_th_unif, plane.data(), plane.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  if (h->ric1_width > 0 &&
+      (hipFuncSetAttribute(reinterpret_cast<const void*>(k_riccati1_ts), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+       hipFuncSetAttribute(reinterpret_cast<const void*>(k_riccati1q_ts), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)) {
+    (void)hipGetLastError();
+    h->ts_narrow = false;
+  }
+  return 0;
+}
+
+// Room for n_sets sets of values (the buffer only grows: more sets always come with their values), the WorkTS copies pointing
+// at it.  Nothing at all when the room is there: an index-only update enqueues one copy.
+int ts_reserve(ltompc_solver* h, const int n_sets) {
+  if (n_sets <= h->ts_cap) return 0;
+  double* fresh = nullptr;
+  if (h->dalloc(&fresh, (size_t)LTOMPC_TABLE_VALUE_ROWS * h->n_table * n_sets)) return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));  // (nothing in flight reads the old buffer when it goes)
+  h->dfree(h->d_ts_vals);
+  h->d_ts_vals = fresh, h->ts_cap = n_sets;
+  return sync_pi_work(h);
 }
 
 // Host form of an entry point on (x, u): both through the d_io staging, `dev` on the device copies (its x_next to dn when asked
@@ -790,6 +880,82 @@ int ltompc_get_table_values(ltompc_handle h, int row, double* values) {
   return 0;
 }
 
+int ltompc_set_table_sets(ltompc_handle h, int n_sets, const double* values, const int* set_of_instance) {
+  const char* who = "ltompc_set_table_sets";
+  if (!h) return fail("null handle");
+  if (n_sets < 0) return fail(std::string(who) + ": n_sets must be >= 0 (0 = back to the handle's tables)");
+  if (n_sets == 0) {
+    if (h->n_sets) h->dv.discard();
+    h->n_sets = 0;
+    return 0;
+  }
+  if (!values && n_sets != h->n_sets)
+    return fail(std::string(who) + ": values == NULL changes the index only and needs n_sets unchanged (" + std::to_string(h->n_sets) + " in effect, " +
+                std::to_string(n_sets) + " given)");
+  if (!set_of_instance && n_sets < h->ts_idx_sets)
+    return fail(std::string(who) + ": set_of_instance == NULL keeps the index, which was written for " + std::to_string(h->ts_idx_sets) + " sets");
+  const size_t per = (size_t)LTOMPC_TABLE_VALUE_ROWS * h->n_table;
+  for (size_t i = 0; values && i < per * n_sets; i++)
+    if (!std::isfinite(values[i]))
+      return fail(std::string(who) + ": non-finite value in set " + std::to_string(i / per) + " (row " + std::to_string(i % per / h->n_table) + ", knot " +
+                  std::to_string(i % h->n_table) + ")");
+  for (int b = 0; set_of_instance && b < h->B; b++)
+    if (set_of_instance[b] < 0 || set_of_instance[b] >= n_sets)
+      return fail(std::string(who) + ": set_of_instance of instance " + std::to_string(b) + " is " + std::to_string(set_of_instance[b]) + ", outside [0, " +
+                  std::to_string(n_sets) + ")");
+  HIPCHECK(hipSetDevice(h->device));
+  if (ts_prepare(h, who) || ts_reserve(h, n_sets)) return -1;
+  if (values) HIPCHECK(hipMemcpyAsync(h->d_ts_vals, values, sizeof(double) * per * n_sets, hipMemcpyHostToDevice, h->stream));
+  if (set_of_instance) {
+    HIPCHECK(hipMemcpyAsync(h->d_ts_idx, set_of_instance, sizeof(int) * h->B, hipMemcpyHostToDevice, h->stream));
+    h->ts_idx_sets = n_sets;
+  }
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->n_sets = n_sets;
+  h->dv.discard();  // (as ltompc_set_table_values: the factorisation and everything computed from it belong to the old tables)
+  return 0;
+}
+
+int ltompc_set_table_sets_dev(ltompc_handle h, int n_sets, const double* values_dev, const int* set_of_instance_dev) {
+  const char* who = "ltompc_set_table_sets_dev";
+  if (!h) return fail("null handle");
+  if (n_sets < 0) return fail(std::string(who) + ": n_sets must be >= 0 (0 = back to the handle's tables)");
+  if (n_sets == 0) {
+    if (h->n_sets) h->dv.discard();
+    h->n_sets = 0;
+    return 0;
+  }
+  if (!values_dev && n_sets != h->n_sets)
+    return fail(std::string(who) + ": values == NULL changes the index only and needs n_sets unchanged (" + std::to_string(h->n_sets) + " in effect, " +
+                std::to_string(n_sets) + " given)");
+  if (!set_of_instance_dev && n_sets < h->ts_idx_sets)
+    return fail(std::string(who) + ": set_of_instance == NULL keeps the index, which was written for " + std::to_string(h->ts_idx_sets) + " sets");
+  HIPCHECK(hipSetDevice(h->device));
+  if (ts_prepare(h, who) || ts_reserve(h, n_sets)) return -1;  // (both synchronise only when they allocate: the first set, more sets than ever)
+  if (values_dev)
+    HIPCHECK(hipMemcpyAsync(h->d_ts_vals, values_dev, sizeof(double) * LTOMPC_TABLE_VALUE_ROWS * h->n_table * n_sets, hipMemcpyDeviceToDevice, h->stream));
+  if (set_of_instance_dev) {  // (clamped into [0, n_sets): whatever the array holds, no look-up leaves the value buffer)
+    hipLaunchKernelGGL(k_ts_index, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, set_of_instance_dev, h->d_ts_idx, h->B, n_sets);
+    HIPCHECK(hipGetLastError());
+    h->ts_idx_sets = n_sets;
+  }
+  h->n_sets = n_sets;
+  h->dv.discard();
+  return 0;
+}
+
+int ltompc_get_table_sets(ltompc_handle h, int* n_sets, double* values, int* set_of_instance) {
+  if (!h) return fail("null handle");
+  if (n_sets) *n_sets = h->n_sets;
+  if (!h->n_sets || (!values && !set_of_instance)) return 0;
+  HIPCHECK(hipSetDevice(h->device));
+  if (values)
+    HIPCHECK(hipMemcpyAsync(values, h->d_ts_vals, sizeof(double) * LTOMPC_TABLE_VALUE_ROWS * h->n_table * h->n_sets, hipMemcpyDeviceToHost, h->stream));
+  if (set_of_instance) HIPCHECK(hipMemcpyAsync(set_of_instance, h->d_ts_idx, sizeof(int) * h->B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) {
   if (!h || !x0_dev) return fail("ltompc_make_step: null argument");
   HIPCHECK(hipSetDevice(h->device));
@@ -810,11 +976,13 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
     hipLaunchKernelGGL(k_shift, dim3(((N + 1) * Bp + 63) / 64), dim3(64), 0, h->stream, h->W, 1);
   }
   if (per_inst) {
-    if (h->pi_solve) hipLaunchKernelGGL(k_init_m_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, (const int*)h->d_cold);
+    if (h->ts_solve) hipLaunchKernelGGL(k_init_m_ts, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wts, (const int*)h->d_cold);
+    else if (h->pi_solve) hipLaunchKernelGGL(k_init_m_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, (const int*)h->d_cold);
     else hipLaunchKernelGGL(k_init_m, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, (const int*)h->d_cold);
     HIPCHECK(hipMemsetAsync(h->d_cold, 0, sizeof(int) * Bp, h->stream));
     h->cold_pending = false;
-  } else if (h->pi_solve) hipLaunchKernelGGL(k_init_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, h->cold_next ? 1 : 0);
+  } else if (h->ts_solve) hipLaunchKernelGGL(k_init_ts, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wts, h->cold_next ? 1 : 0);
+  else if (h->pi_solve) hipLaunchKernelGGL(k_init_pi, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, h->cold_next ? 1 : 0);
   else hipLaunchKernelGGL(k_init, dim3((N * Bp + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, h->cold_next ? 1 : 0);
   HIPCHECK(hipMemsetAsync(h->W.active, 0, sizeof(int) * ((size_t)h->max_iter + 2), h->stream));
   HIPCHECK(hipMemsetAsync(h->W.ls_count, 0, 2 * sizeof(int), h->stream));
@@ -963,7 +1131,8 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
   if (!h || !x_dev) return fail("ltompc_rollout: null argument");
   if (n_ticks < 1 || n_sub < 1) return fail("ltompc_rollout: n_ticks and n_sub must be >= 1");
   if (h->K.o.warm_shift) return fail("ltompc_rollout: options.warm_shift is not supported by the rollout");
-  if (h->eval8) return fail("ltompc_rollout: latency-mode handles (8-lanes-per-slot kernels) are not supported by the rollout");
+  if (h->eval8 && !h->n_sets)  // (with table sets the handle runs the thread-per-slot kernels anyway)
+    return fail("ltompc_rollout: latency-mode handles (8-lanes-per-slot kernels) are not supported by the rollout");
   HIPCHECK(hipSetDevice(h->device));
   if (ensure_unpacked(h)) return -1;  // the rollout works in the caller's order (index-list compaction only)
   h->dv.discard();
@@ -1021,14 +1190,17 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
     ROLLCHECK(hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), h->stream));
     if (first && h->cold_pending) {  // cold or warm per instance (warm_state.h), in the first pass: every instance starts its first solve there
       hipLaunchKernelGGL(k_roll_mark_m, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, (const double*)x_dev, h->K.o.resto_sticky, (const int*)h->d_cold);
-      if (h->pi_solve) hipLaunchKernelGGL(k_roll_init_m_pi, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, la, (const int*)h->d_cold);
+      if (h->ts_solve) hipLaunchKernelGGL(k_roll_init_m_ts, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wts, la, (const int*)h->d_cold);
+      else if (h->pi_solve) hipLaunchKernelGGL(k_roll_init_m_pi, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, la, (const int*)h->d_cold);
       else hipLaunchKernelGGL(k_roll_init_m, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, la, (const int*)h->d_cold);
       ROLLCHECK(hipMemsetAsync(h->d_cold, 0, sizeof(int) * Bp, h->stream));
       h->cold_pending = false;
     } else {
     hipLaunchKernelGGL(k_roll_mark, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->W, (const double*)x_dev, h->K.o.resto_sticky,
                        (first && h->cold_next) ? 1 : 0);  // (after set_initial_guess there is no solve before this one to take stock of)
-    if (h->pi_solve)
+    if (h->ts_solve)
+      hipLaunchKernelGGL(k_roll_init_ts, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wts, la, (first && h->cold_next) ? 1 : 0);
+    else if (h->pi_solve)
       hipLaunchKernelGGL(k_roll_init_pi, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_Wpi, la, (first && h->cold_next) ? 1 : 0);
     else hipLaunchKernelGGL(k_roll_init, dim3((N * np + 63) / 64), dim3(64), 0, h->stream, h->d_K, h->d_W, la, (first && h->cold_next) ? 1 : 0);
     }
@@ -1046,7 +1218,10 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
       hipStream_t ps = h->plant_streams[it % h->n_plant_streams];
       ROLLCHECK(hipEventRecord(h->ev_fin[slot], h->stream));
       ROLLCHECK(hipStreamWaitEvent(ps, h->ev_fin[slot], 0));
-      if (h->pi_solve)
+      if (h->ts_solve)
+        hipLaunchKernelGGL(k_roll_plant_ts, dim3((n_launch + 63) / 64), dim3(64), 0, ps, h->K, h->Wts, x_dev, h->K.o.t_step, n_sub, (const int*)(d_cnt + 1),
+                           (const int*)d_list);
+      else if (h->pi_solve)
         hipLaunchKernelGGL(k_roll_plant_pi, dim3((n_launch + 63) / 64), dim3(64), 0, ps, h->K, h->Wpi, x_dev, h->K.o.t_step, n_sub, (const int*)(d_cnt + 1),
                            (const int*)d_list);
       else
@@ -1208,7 +1383,10 @@ int ltompc_plant_step_dev(ltompc_handle h, const double* x_dev, const double* u_
   if (!h || !x_dev || !u_dev || !x_next_dev) return fail("ltompc_plant_step: null argument");
   if (n_sub < 1) return fail("ltompc_plant_step: n_sub must be >= 1");
   HIPCHECK(hipSetDevice(h->device));
-  if (h->pi_pend)  // (the rows in effect: those set last)
+  if (h->n_sets)  // (the sets in effect, with the rows in effect or the handle's own params)
+    hipLaunchKernelGGL(k_plant_ts, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, (const double*)(h->pi_pend ? h->d_th_pend : h->d_th_unif),
+                       (const double*)h->d_ts_vals, (const int*)h->d_ts_idx, h->Bp, h->B, x_dev, u_dev, h->K.o.t_step, n_sub, x_next_dev);
+  else if (h->pi_pend)  // (the rows in effect: those set last)
     hipLaunchKernelGGL(k_plant_pi, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, (const double*)h->d_th_pend, h->Bp, h->B, x_dev, u_dev,
                        h->K.o.t_step, n_sub, x_next_dev);
   else hipLaunchKernelGGL(k_plant, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, h->B, x_dev, u_dev, h->K.o.t_step, n_sub, x_next_dev);

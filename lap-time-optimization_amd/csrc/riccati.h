@@ -32,7 +32,7 @@ __device__ __forceinline__ int node0_rule(const ltompc_options& o, const double 
 // block for the entry of the restoration phase.
 // What it reads (ST_EPS, x0) comes in registers: d_head8 fetches them with the rest of the instance's state, so that no load
 // follows the head's stores.
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work& W, const int b, const double rho, const double eps_now,
                                                     const double (&x0)[8]) {
   double* st = W.st;
@@ -43,7 +43,7 @@ __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work&
   STD(ST_RHO) = rho, STD(ST_MU) = mu0, STD(ST_EPS_NEXT) = eps;
   if (eps != eps_now) {  // (d_pick, which switches the smoothing otherwise, does not see the instance in this launch)
     STD(ST_EPS) = eps;
-    STD(ST_C00) = cost_eval(inst_params<PI>(K.p, W, b), K.T, eps, x0, false, nullptr, nullptr);
+    STD(ST_C00) = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, x0, false, nullptr, nullptr);
   }
   STI(SI_REINIT) = 1;
   STI(SI_NFILT) = 0, STD(ST_THETA0) = -1.0;
@@ -53,13 +53,13 @@ __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work&
 }
 
 // ... for a caller that has not fetched them (k_riccati)
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ void restart_from_primal(const Consts& K, const Work& W, const int b, const double rho) {
   double* st = W.st;
   double x0[8];
 #pragma unroll
   for (int q = 0; q < 8; q++) x0[q] = W.x0[(size_t)q * W.Bp + b];
-  restart_from_primal<PI>(K, W, b, rho, STD(ST_EPS), x0);
+  restart_from_primal<PI, TS>(K, W, b, rho, STD(ST_EPS), x0);
 }
 
 // ------------------------------------------------------------------------------------------ k_riccati
@@ -390,7 +390,7 @@ __global__ void __launch_bounds__(64) k_riccati(const Consts* __restrict__ Kp, c
 // produce the same bits).  Returns false when no lane of the wavefront has a sweep to do.
 constexpr int HEAD_Q = 5;   // trips of the reduction over k = i, i + 8, ... in the first batch of loads: N = 40 in one
 constexpr int HEAD_S = 20;  // stages of the ordered sums per round trip
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const int i, const int b, const bool valid,
                                         const int active_slot, bool& live, bool& retry, double& mu) {
   const int N = W.N;
@@ -529,7 +529,7 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
         STI(SI_STEP) = 0, STI(SI_SKIP_EVAL) = 0;
       }
       if (escalate) {
-        restart_from_primal<PI>(K, W, b, fmin(rho * o.resto_rho_factor, o.resto_rho_max), eps_now, x0);
+        restart_from_primal<PI, TS>(K, W, b, fmin(rho * o.resto_rho_factor, o.resto_rho_max), eps_now, x0);
         STI(SI_NRESTO) = nresto + 1;
       }
     }
@@ -582,7 +582,7 @@ __device__ __forceinline__ bool d_head8(const Consts& K, const Work& W, const in
       STD(ST_TAU) = fmax(o.tau_min, 1.0 - mu * iS);
       if (fallback) {
         STI(SI_FBARMED) = 0, STI(SI_NFALLBACK) = nfallback + 1;
-        restart_from_primal<PI>(K, W, b, rho, eps_now, x0);
+        restart_from_primal<PI, TS>(K, W, b, rho, eps_now, x0);
       }
     }
     if (fallback || (stuck && !recoverable)) live = false;
@@ -616,7 +616,7 @@ struct FwdRegs {
 // SENS (sensitivity.h): the head-less factorisation at the final iterate - no head, delta_w = 0, one sweep, no schedule,
 // no status writes, no rollout; sens_live selects the instances whose gains are stored, sens_inertia[b] gets 1 when every
 // stage's Huu passed the inertia test.  The solver's instantiation (SENS = false) is unchanged.
-template <bool SENS = false, bool PI = false>
+template <bool SENS = false, bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLds& L, const int g, const int i, const int b,
                                            const bool valid, const int active_slot, const int max_sweeps, const bool sens_live = false,
                                            int* sens_inertia = nullptr) {
@@ -633,7 +633,7 @@ __device__ __forceinline__ void d_riccati8(const Consts& K, const Work& W, RicLd
       return;
     }
   } else {
-    if (!d_head8<PI>(K, W, i, b, valid, active_slot, live, retry, mu)) return;
+    if (!d_head8<PI, TS>(K, W, i, b, valid, active_slot, live, retry, mu)) return;
   }
   // ---- backward sweep (whole wave in lock-step; an instance whose Huu fails retries with a larger delta_w,
   //      the others recompute the same numbers)
@@ -1004,7 +1004,7 @@ __device__ __forceinline__ void load_stage1(const StageLds& S, const double p0, 
   s.v[0] = k > 0 ? v0 : p0, s.v[1] = k > 0 ? v1 : p1;
 }
 
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_riccati1(const Consts& K, const Work& W, Ric1Lds& L, const StageLds& S, const int g, const int i, const int b,
                                            const bool valid, const int active_slot, const int max_sweeps) {
   const int N = W.N;
@@ -1017,7 +1017,7 @@ __device__ __forceinline__ void d_riccati1(const Consts& K, const Work& W, Ric1L
 #define RTOCK(q) if (rprof) { const long long t1 = clock64(); W.DBG[q] += (double)(t1 - rt0); rt0 = t1; }
   bool live, retry;
   double mu;
-  if (!d_head8<PI>(K, W, i, b, valid, active_slot, live, retry, mu)) return;
+  if (!d_head8<PI, TS>(K, W, i, b, valid, active_slot, live, retry, mu)) return;
   // ---- backward sweep (whole wave in lock-step; an instance whose Huu fails retries with a larger delta_w,
   //      the others recompute the same numbers)
   const double r2[2] = {2.0 * inst_r_du<PI>(K.p, W, b, 0), 2.0 * inst_r_du<PI>(K.p, W, b, 1)};
@@ -1315,7 +1315,7 @@ __host__ __device__ constexpr size_t ric1q_lds_bytes(int N) { return sizeof(doub
 #else
 #define WG_SYNC_LDS() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #endif
-template <bool PI = false>
+template <bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1qLds& X, const StageLds& S, const int t, const int b,
                                             const int active_slot, const int max_sweeps) {
   const int N = W.N;
@@ -1333,7 +1333,7 @@ __device__ __forceinline__ void d_riccati1q(const Consts& K, const Work& W, Ric1
   int tries = 0;
   bool numerical = false;
   if (w == 0) {
-    const bool go = d_head8<PI>(K, W, i, b, g == 0, active_slot, live, retry, mu);
+    const bool go = d_head8<PI, TS>(K, W, i, b, g == 0, active_slot, live, retry, mu);
     psc = pen_scale(STD(ST_RHO));  // penalty scale (layout.h): the regularisation schedule in its units
     dw_last = STD(ST_DW_LAST);
     double delta_w = STD(ST_FORCE_REG);
@@ -1745,6 +1745,45 @@ __global__ void __launch_bounds__(64) k_riccati1_pi(Consts K, WorkPI W, Launch l
   StageLds S{lds1, lds1 + (size_t)N * QP_NF, lds1 + (size_t)N * (QP_NF + 2)};
   Ric1Lds& L = *reinterpret_cast<Ric1Lds*>(lds1 + (size_t)N * (QP_NF + 24));
   d_riccati1<true>(K, W, L, S, g, i, la.act[blockIdx.x], g == 0, it_index, max_sweeps);
+}
+
+// ... and per-instance table sets (W.TSV / W.TSI, DESIGN.md §16: the head evaluates lterm(x_0) on the instance's v_ref row when a
+// restart from the primal point changes the smoothing)
+__global__ void __launch_bounds__(64) k_riccati8_ts(Consts K, WorkTS W, Launch la, int it_index, int max_sweeps) {
+  __shared__ RicLds L;
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  const int jj = blockIdx.x * 8 + g;
+  const bool valid = jj < la.nact[0];
+  d_riccati8<false, true, true>(K, W, L, g, i, la.act[valid ? jj : 0], valid, it_index, max_sweeps);
+}
+__global__ void __launch_bounds__(256) k_riccati1q_ts(Consts K, WorkTS W, Launch la, int it_index, int max_sweeps) {
+#if defined(LTOMPC_HARNESS_WORKGROUP)
+  double* const lds1q = static_cast<double*>(lt_dyn_lds);  // ric1q_lds_bytes(N) at its exact size, allocated per block by the harness
+#elif defined(LTOMPC_HOST_HARNESS)
+  static double lds1q[1];  // (a shim without the lock-step workgroup only compiles this)
+#else
+  extern __shared__ double lds1q[];
+#endif
+  if ((int)blockIdx.x >= la.nact[0]) return;
+  const int N = W.N;
+  StageLds S{lds1q, lds1q + (size_t)N * QP_NF, lds1q + (size_t)N * (QP_NF + 2)};
+  Ric1qLds& X = *reinterpret_cast<Ric1qLds*>(lds1q + (size_t)N * (QP_NF + 24));
+  d_riccati1q<true, true>(K, W, X, S, threadIdx.x, la.act[blockIdx.x], it_index, max_sweeps);
+}
+__global__ void __launch_bounds__(64) k_riccati1_ts(Consts K, WorkTS W, Launch la, int it_index, int max_sweeps) {
+#if defined(LTOMPC_HARNESS_WAVEFRONT)
+  double* const lds1 = static_cast<double*>(lt_dyn_lds);  // ric1_lds_bytes(N) at its exact size, allocated per block by the harness
+#elif defined(LTOMPC_HOST_HARNESS)
+  static double lds1[1];  // (a shim without the lock-step wavefront never runs this)
+#else
+  extern __shared__ double lds1[];
+#endif
+  const int lane = threadIdx.x, g = lane & 7, i = lane >> 3;
+  if ((int)blockIdx.x >= la.nact[0]) return;
+  const int N = W.N;
+  StageLds S{lds1, lds1 + (size_t)N * QP_NF, lds1 + (size_t)N * (QP_NF + 2)};
+  Ric1Lds& L = *reinterpret_cast<Ric1Lds*>(lds1 + (size_t)N * (QP_NF + 24));
+  d_riccati1<true, true>(K, W, L, S, g, i, la.act[blockIdx.x], g == 0, it_index, max_sweeps);
 }
 
 }  // namespace ltompc

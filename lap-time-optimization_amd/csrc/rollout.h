@@ -60,6 +60,17 @@ __global__ void k_roll_init_pi(const Consts* __restrict__ Kp, const WorkPI* __re
   if (W.si[(size_t)SI_PHASE * W.Bp + b] != PH_INIT) return;
   d_init_slot<true>(K, W, k, b, cold);
 }
+// ... and per-instance table sets (W.TSV / W.TSI)
+__global__ void k_roll_init_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la, int cold) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  int j = tid % la.n_pad, k = tid / la.n_pad;
+  if (k >= W.N || j >= la.nact[0]) return;
+  const int b = la.act[j];
+  if (W.si[(size_t)SI_PHASE * W.Bp + b] != PH_INIT) return;
+  d_init_slot<true, true>(K, W, k, b, cold);
+}
 // end of an iteration: INIT -> SOLVING; SOLVING and converged -> log, u_prev := u0, PLANT.  count: instances not FINAL.
 __global__ void k_roll_finish(Work W, Launch la, double* __restrict__ u_log, int* __restrict__ st_log, int* __restrict__ it_log, int n_ticks,
                               int* __restrict__ count, int* __restrict__ plant_list) {
@@ -112,6 +123,24 @@ __global__ void __launch_bounds__(64) k_roll_plant_pi(Consts K, WorkPI W, double
 #pragma unroll
   for (int i = 0; i < 8; i++) x[i] = x_rm[(size_t)b * 8 + i];
   d_plant<true>(K, x, uu, dt, n_sub, y, W.TH, W.Bp, b);  // (the rollout runs in the caller's order: slot b = instance b)
+#pragma unroll
+  for (int i = 0; i < 8; i++) x_rm[(size_t)b * 8 + i] = y[i];
+  const int left = W.si[(size_t)SI_TICKS * W.Bp + b] - 1;
+  W.si[(size_t)SI_TICKS * W.Bp + b] = left;
+  if (left <= 0) W.si[(size_t)SI_FINAL * W.Bp + b] = 1;
+  __threadfence();  // (x_rm, ticks before the phase)
+  *ph = left > 0 ? PH_READY : PH_FINAL;
+}
+// ... and per-instance table sets (W.TSV / W.TSI)
+__global__ void __launch_bounds__(64) k_roll_plant_ts(Consts K, WorkTS W, double* x_rm, double dt, int n_sub, const int* __restrict__ n_list, const int* __restrict__ list) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_list[0]) return;
+  const int b = list[j];
+  volatile int* ph = &W.si[(size_t)SI_PHASE * W.Bp + b];
+  double x[8], y[8], uu[2] = {W.uprev[b], W.uprev[(size_t)W.Bp + b]};
+#pragma unroll
+  for (int i = 0; i < 8; i++) x[i] = x_rm[(size_t)b * 8 + i];
+  d_plant<true, decltype(W.TH), true>(K, x, uu, dt, n_sub, y, W.TH, W.Bp, b, W.TSV, W.TSI[b]);  // (the rollout runs in the caller's order: slot b = instance b)
 #pragma unroll
   for (int i = 0; i < 8; i++) x_rm[(size_t)b * 8 + i] = y[i];
   const int left = W.si[(size_t)SI_TICKS * W.Bp + b] - 1;

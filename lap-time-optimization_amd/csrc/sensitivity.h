@@ -64,6 +64,16 @@ __global__ void __launch_bounds__(64) k_sens_eval_pi(const Consts* __restrict__ 
   if (k >= W.N || b >= W.B) return;
   d_eval<BP, false, true>(K, W, k, b, true);
 }
+// ... and per-instance table sets (W.TSV / W.TSI; the head-less sweep and the forward pass read no table: the _pi ones)
+template <class BP>
+__global__ void __launch_bounds__(64) k_sens_eval_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wsp) {
+  const Consts& K = *Kp;
+  const Work& W = *Wsp;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = tid % W.Bp, k = tid / W.Bp;
+  if (k >= W.N || b >= W.B) return;
+  d_eval<BP, false, true, true>(K, W, k, b, true);
+}
 
 // si_solve: the solver's own si planes (read only).  An instance is differentiated when the solver's status (before the
 // node-0 rule) is SOLVED or ACCEPTABLE and it was not re-initialised; inertia[b] = 1 when every stage's Huu is positive definite

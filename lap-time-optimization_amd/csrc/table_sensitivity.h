@@ -302,7 +302,7 @@ __device__ __forceinline__ double tab_kappa_column(const Slot& S, const M8Blocks
   return acc;
 }
 
-template <class BP, bool PI = false>
+template <class BP, bool PI = false, bool TS = false>
 __device__ __forceinline__ void d_tab_cond(const Consts& K, const Work& W, const int k, const int b, const double* __restrict__ TJ,
                                            const int* __restrict__ ok_in, double* __restrict__ slot_grad) {
   const int N = W.N;
@@ -328,7 +328,7 @@ __device__ __forceinline__ void d_tab_cond(const Consts& K, const Work& W, const
   if (k + 1 <= N - 1) {
     const int m_nl = for_each_bound<BP>(K.p, [](int, int, int, double, double) {});
     double gv[3], gs[3], gn[3], gm[3], hss[3], hmm[3], Sg[3], nq[3];
-    cons_eval(K.p, K.T, eps, xp, gv, gs, gn, gm, hss, hmm);
+    cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, xp, gv, gs, gn, gm, hss, hmm);
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       const double t = PL(W.T, m_nl + q, k, N), el = rho > 0.0 ? PL(W.T, K.bd.ni + q, k, N) : 0.0;
@@ -343,7 +343,7 @@ __device__ __forceinline__ void d_tab_cond(const Consts& K, const Work& W, const
     node[3] = -(nq[1] + nq[2]) * an[0];
     // stage cost q_v (vx - cv v_ref(s))^2: gradient (-2 q_v e cv v', 2 q_v e) over (s, vx)
     double vr, vr1, vr2;
-    lut_eval(K.T.s_arc, K.T.v_ref, K.T.n, K.T.g0_arc, K.T.inv_arc, K.T.period, xp[0], eps, vr, vr1, vr2);
+    lut_eval(K.T.s_arc, inst_tables<TS>(K.T, W, b).v_ref, K.T.n, K.T.g0_arc, K.T.inv_arc, K.T.period, xp[0], eps, vr, vr1, vr2);
     const double cv = K.p.vref_scale, ee = xp[3] - cv * vr;
     node[4] = 2.0 * K.p.q_v * cv * (cv * vr1 * an[0] - an[3]);
     node[5] = -2.0 * K.p.q_v * ee * cv * an[0];
@@ -352,8 +352,8 @@ __device__ __forceinline__ void d_tab_cond(const Consts& K, const Work& W, const
   for (int q = 0; q < 6; q++) out[TS_NL + q] = node[q];
   // ---- the four kappa columns.  E1, E2 and the c-block Hc exactly as d_psens_cond forms them (same calls, same order)
   double kc, kpc, kx, kpx, cv_;
-  lut_eval(K.T.s_kappa, K.T.kappa, K.T.n, K.T.g0_kappa, K.T.inv_kappa, K.T.period, c[0], eps, kc, kpc, cv_);
-  lut_eval(K.T.s_kappa, K.T.kappa, K.T.n, K.T.g0_kappa, K.T.inv_kappa, K.T.period, xp[0], eps, kx, kpx, cv_);
+  lut_eval(K.T.s_kappa, inst_tables<TS>(K.T, W, b).kappa, K.T.n, K.T.g0_kappa, K.T.inv_kappa, K.T.period, c[0], eps, kc, kpc, cv_);
+  lut_eval(K.T.s_kappa, inst_tables<TS>(K.T, W, b).kappa, K.T.n, K.T.g0_kappa, K.T.inv_kappa, K.T.period, xp[0], eps, kx, kpx, cv_);
   Slot S;
   {
     double lam[8], f[8], J[48];
@@ -361,12 +361,12 @@ __device__ __forceinline__ void d_tab_cond(const Consts& K, const Work& W, const
     for (int i = 0; i < 8; i++) lam[i] = PL(W.L1, i, k, N);
 #pragma unroll
     for (int i = 0; i < 36; i++) S.Hc[i] = 0.0;
-    rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, c, f, J, lam, hdt, S.Hc);
+    rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, c, f, J, lam, hdt, S.Hc);
 #pragma unroll
     for (int i = 0; i < 64; i++) S.E1[i] = 0.0, S.E2[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < 48; i++) S.E1[i] = hdt * J[i];
-    rhs_derivs(inst_params<PI>(K.p, W, b), K.T, eps, xp, f, J, nullptr, 0.0, nullptr);
+    rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, xp, f, J, nullptr, 0.0, nullptr);
 #pragma unroll
     for (int i = 0; i < 48; i++) S.E2[i] = hdt * J[i];
 #pragma unroll
@@ -422,6 +422,17 @@ __global__ void __launch_bounds__(64) k_tab_cond_pi(const Consts* __restrict__ K
   if (k >= W.N || b >= W.B) return;
   d_tab_cond<BP, true>(K, W, k, b, TJ, ok_in, slot_grad);
 }
+// ... and per-instance table sets (W.TSV / W.TSI): every look-up on the rows of the instance's set
+template <class BP>
+__global__ void __launch_bounds__(64) k_tab_cond_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, const double* __restrict__ TJ,
+                                                    const int* __restrict__ ok_in, double* __restrict__ slot_grad) {
+  const Consts& K = *Kp;
+  const Work& W = *Wp;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = tid % W.Bp, k = tid / W.Bp;
+  if (k >= W.N || b >= W.B) return;
+  d_tab_cond<BP, true, true>(K, W, k, b, TJ, ok_in, slot_grad);
+}
 
 // ------------------------------------------------------------------------------------------ k_tab_scatter
 // thread = (look-up point p, interval k, instance b), p = 0: kappa at s(c_k), 1: kappa at s(x_{k+1}), 2: n_left, n_right, v_ref at
@@ -441,6 +452,38 @@ __global__ void __launch_bounds__(256) k_tab_scatter(const Consts* __restrict__ 
   const double s = p == 0 ? PL(W.C, 0, k, N) : PL(W.X, 0, k + 1, N + 1);
   const double* sg = slot_grad + (ob * N + k) * TS_NS;
   const int n = T.n;
+  LutBasis R;
+  if (p < 2) lut_basis(T.s_kappa, n, T.g0_kappa, T.inv_kappa, T.period, s, eps, R);
+  else lut_basis(T.s_arc, n, T.g0_arc, T.inv_arc, T.period, s, eps, R);
+  const int rows = p < 2 ? 1 : 3;
+  for (int r = 0; r < rows; r++) {
+    const int col = p < 2 ? 2 * p : TS_NL + 2 * r, row = p < 2 ? 0 : 1 + r;
+    const double gval = sg[col], gslope = sg[col + 1];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const double t = gval * R.wv[j] + gslope * R.ws[j];
+      if (t != 0.0) atomicAdd(grad_tables + (size_t)row * n + R.idx[j], t);
+    }
+  }
+}
+// ... on a handle with per-instance table sets: grad_tables is [n_sets][TAB_ROWS][n] and an instance adds into the
+// block of its set, tsi[its caller's index].  A copy of the kernel above (tests/test_table_sets_resources.py checks the text): through a
+// shared __device__ function the uniform kernel's instructions changed (operand order of its multiplies).
+__global__ void __launch_bounds__(256) k_tab_scatter_ts(const Consts* __restrict__ Kp, Work W, const int* __restrict__ ok_in,
+                                                        const double* __restrict__ slot_grad, double* __restrict__ grad_tables,
+                                                        const int* __restrict__ tsi) {
+  const Tables& T = Kp->T;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = W.N;
+  const int b = (int)(tid % W.Bp), k = (int)((tid / W.Bp) % N), p = (int)(tid / ((size_t)W.Bp * N));
+  if (p > 2 || b >= W.B) return;
+  const size_t ob = W.orig[b];
+  if (!ok_in[ob]) return;
+  const double eps = W.st[(size_t)ST_EPS * W.Bp + b];
+  const double s = p == 0 ? PL(W.C, 0, k, N) : PL(W.X, 0, k + 1, N + 1);
+  const double* sg = slot_grad + (ob * N + k) * TS_NS;
+  const int n = T.n;
+  grad_tables += (size_t)tsi[ob] * TAB_ROWS * n;
   LutBasis R;
   if (p < 2) lut_basis(T.s_kappa, n, T.g0_kappa, T.inv_kappa, T.period, s, eps, R);
   else lut_basis(T.s_arc, n, T.g0_arc, T.inv_arc, T.period, s, eps, R);

@@ -35,15 +35,16 @@ __global__ void k_load_x0_m(Work W, const double* __restrict__ x0_rm, int sticky
   const size_t r = W.orig[b];
   d_load_x0(W, x0_rm, b, r, sticky, cold[r] ? 0 : 1);
 }
-template <bool PI>
+template <bool PI, bool TS = false>
 __device__ __forceinline__ void d_init_m(const Consts& K, const Work& W, const int* __restrict__ cold) {
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int b = tid % W.Bp, k = tid / W.Bp;
   if (k >= W.N || b >= W.B) return;
-  d_init_slot<PI>(K, W, k, b, cold[W.orig[b]] ? 1 : 0);
+  d_init_slot<PI, TS>(K, W, k, b, cold[W.orig[b]] ? 1 : 0);
 }
 __global__ void k_init_m(const Consts* __restrict__ Kp, const Work* __restrict__ Wp, const int* __restrict__ cold) { d_init_m<false>(*Kp, *Wp, cold); }
 __global__ void k_init_m_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, const int* __restrict__ cold) { d_init_m<true>(*Kp, *Wp, cold); }
+__global__ void k_init_m_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, const int* __restrict__ cold) { d_init_m<true, true>(*Kp, *Wp, cold); }
 
 // the first pass of a rollout (it runs in the caller's order: slot b = instance b)
 __global__ void k_roll_mark_m(Work W, const double* x_rm, int sticky, const int* __restrict__ cold) {
@@ -55,20 +56,23 @@ __global__ void k_roll_mark_m(Work W, const double* x_rm, int sticky, const int*
   d_load_x0(W, x_rm, b, (size_t)b, sticky, cold[b] ? 0 : 1);
   *ph = PH_INIT;
 }
-template <bool PI>
+template <bool PI, bool TS = false>
 __device__ __forceinline__ void d_roll_init_m(const Consts& K, const Work& W, const Launch& la, const int* __restrict__ cold) {
   int tid = blockIdx.x * blockDim.x + threadIdx.x;
   int j = tid % la.n_pad, k = tid / la.n_pad;
   if (k >= W.N || j >= la.nact[0]) return;
   const int b = la.act[j];
   if (W.si[(size_t)SI_PHASE * W.Bp + b] != PH_INIT) return;
-  d_init_slot<PI>(K, W, k, b, cold[W.orig[b]] ? 1 : 0);
+  d_init_slot<PI, TS>(K, W, k, b, cold[W.orig[b]] ? 1 : 0);
 }
 __global__ void k_roll_init_m(const Consts* __restrict__ Kp, const Work* __restrict__ Wp, Launch la, const int* __restrict__ cold) {
   d_roll_init_m<false>(*Kp, *Wp, la, cold);
 }
 __global__ void k_roll_init_m_pi(const Consts* __restrict__ Kp, const WorkPI* __restrict__ Wp, Launch la, const int* __restrict__ cold) {
   d_roll_init_m<true>(*Kp, *Wp, la, cold);
+}
+__global__ void k_roll_init_m_ts(const Consts* __restrict__ Kp, const WorkTS* __restrict__ Wp, Launch la, const int* __restrict__ cold) {
+  d_roll_init_m<true, true>(*Kp, *Wp, la, cold);
 }
 
 // ------------------------------------------------------------------------------------------ masked reset

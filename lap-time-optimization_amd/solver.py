@@ -36,6 +36,8 @@ class BatchedMPC:
         self._pfb = None  # du0_dtheta of that solve, fetched by the first feedback(theta=...)
         self._theta_rows = None  # per-instance rows set (set_theta), (B, 16), None: the handle's params, _DEV_ROWS: set_theta_dev
         self._theta_solved = None  # ... those of the last solve (feedback(theta=...) expands around them)
+        self.n_table_sets = 0  # per-instance table sets in effect (set_table_sets; 0: the handle's own tables)
+        self._set_index_for = 1  # ... the number of sets their index was written for (1: the zeros it starts with)
         self._uprev_next = np.zeros((self.B, NU))
         self.device = f"cuda:{int(device)}"  # torch's name of the handle's device (the one device check of autograd.py)
         self.solve_count = 0  # solves and initial guesses so far: what a derivative of "the last solve" refers to (autograd.py)
@@ -452,6 +454,92 @@ class BatchedMPC:
             check(lib().ltompc_get_table_values(self._h, r, dptr(out[r])))
         return out
 
+    # ---- per-instance table sets (ltompc_set_table_sets) ---------------------------------------------------
+    def set_table_sets(self, values=None, index=None):
+        """Per-instance track tables: values (n_sets, 4, n_table) finite, the value rows TABLE_ROW_NAMES of every set on the
+        handle's own grids, and index (B,) integers in [0, n_sets), the set of every instance.  Instance b then solves, steps
+        its plant and rolls out exactly (bit for bit) as on a handle created with set index[b] written into the tables'
+        value rows (in thread-per-slot evaluation mode, latency_mode = 2, which handles with sets always run).
+        values=None: the sets stay, only the index changes; index=None: the index stays (all zeros before the first one);
+        both None: back to the handle's own tables, which set_table_values keeps writing meanwhile.
+        Timing as set_table_values: from the next solve, plant step and rollout on; the warm start is kept; the last solve's
+        derivatives are discarded.  With sets in effect the derivatives w.r.t. theta, plant_sensitivities, the loop_* passes
+        and adjoint_tables raise; adjoint_table_sets gives one table gradient per set."""
+        if values is None and index is None:
+            check(lib().ltompc_set_table_sets(self._h, 0, None, None))
+            self.n_table_sets = 0
+            self._tables_changed()
+            return
+        n_sets = self.n_table_sets
+        if values is not None:
+            values = _table_sets(values, self._tab.shape[1])
+            n_sets = values.shape[0]
+        elif not n_sets:
+            raise ValueError("set_table_sets: values=None keeps the sets in effect, and there are none")
+        if index is not None:
+            index = _set_index(index, self.B, n_sets)
+        elif n_sets < self._set_index_for:
+            raise ValueError(f"set_table_sets: index=None keeps the index, which was written for {self._set_index_for} sets (now {n_sets})")
+        check(lib().ltompc_set_table_sets(self._h, n_sets, dptr(values) if values is not None else None,
+                                          iptr(index) if index is not None else None))
+        self.n_table_sets = n_sets
+        if index is not None:
+            self._set_index_for = n_sets
+        self._tables_changed()
+
+    def set_table_sets_dev(self, n_sets: int, values_ptr: int = 0, index_ptr: int = 0):
+        """set_table_sets from device arrays (ltompc_set_table_sets_dev): (n_sets, 4, n_table) float64 and (B,) int32, either 0
+        to keep what is there (values only with n_sets unchanged); n_sets = 0 drops the sets.  Enqueued on the handle's stream.
+        The values are NOT checked; the index is clamped into [0, n_sets) by the kernel that copies it."""
+        n_sets = int(n_sets)
+        if n_sets < 0:
+            raise ValueError(f"set_table_sets_dev: n_sets must be >= 0, got {n_sets}")
+        if n_sets and not values_ptr and n_sets != self.n_table_sets:
+            raise ValueError(f"set_table_sets_dev: values_ptr=0 keeps the sets in effect and needs n_sets unchanged ({self.n_table_sets} in effect, {n_sets} given)")
+        if n_sets and not index_ptr and n_sets < self._set_index_for:
+            raise ValueError(f"set_table_sets_dev: index_ptr=0 keeps the index, which was written for {self._set_index_for} sets (now {n_sets})")
+        check(lib().ltompc_set_table_sets_dev(self._h, n_sets, C.c_void_p(values_ptr or None), C.c_void_p(index_ptr or None)))
+        self.n_table_sets = n_sets
+        if n_sets and index_ptr:
+            self._set_index_for = n_sets
+        self._tables_changed()
+
+    def table_sets(self):
+        """The sets in effect: (values (n_sets, 4, n_table) in TABLE_ROW_NAMES order, index (B,) int32), or None without sets."""
+        n = C.c_int(0)
+        check(lib().ltompc_get_table_sets(self._h, C.byref(n), None, None))
+        if not n.value:
+            return None
+        values, index = np.empty((n.value, len(TABLE_ROW_NAMES), self._tab.shape[1])), np.empty(self.B, dtype=np.int32)
+        check(lib().ltompc_get_table_sets(self._h, C.byref(n), dptr(values), iptr(index)))
+        return values, index
+
+    def adjoint_table_sets(self, gX=None, gU=None, slots: bool = False):
+        """adjoint_tables on a handle with table sets: grad_sets (n_sets, 4, n_table), block g summed over the ok instances of
+        set g (zeros for a set without instances), in place of grad_tables; names, ok and, with slots=True, slot_grad as there."""
+        B, N = self.B, self.N
+        if not self.n_table_sets:
+            raise ValueError("adjoint_table_sets: the handle has no table sets (set_table_sets); its table gradient is adjoint_tables()")
+        if gX is not None:
+            gX = _shaped("adjoint_table_sets", "gX", gX, (B, N + 1, NX))
+        if gU is not None:
+            gU = _shaped("adjoint_table_sets", "gU", gU, (B, N, NU))
+        gs, ok = np.empty((self.n_table_sets, len(TABLE_ROW_NAMES), self._tab.shape[1])), np.empty(B, dtype=np.int32)
+        sg = np.empty((B, N, len(TABLE_SLOT_NAMES))) if slots else None
+        check(lib().ltompc_get_adjoint_table_sets(self._h, dptr(gX) if gX is not None else None, dptr(gU) if gU is not None else None,
+                                                  dptr(gs), dptr(sg) if slots else None, iptr(ok)))
+        out = dict(grad_sets=gs, names=TABLE_ROW_NAMES, ok=ok != 0)
+        if slots:
+            out.update(slot_grad=sg, slot_names=TABLE_SLOT_NAMES)
+        return out
+
+    def adjoint_table_sets_dev(self, gX_ptr: int, gU_ptr: int, grad_sets_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0, add: bool = False):
+        """adjoint_tables_dev on a handle with table sets: grad_sets (n_sets,4,n_table) doubles in place of grad_tables
+        (add=True: added to the array, ltompc_adjoint_table_sets_add_dev)."""
+        fn = lib().ltompc_adjoint_table_sets_add_dev if add else lib().ltompc_adjoint_table_sets_dev
+        check(fn(self._h, C.c_void_p(gX_ptr or None), C.c_void_p(gU_ptr or None), C.c_void_p(grad_sets_ptr or None),
+                 C.c_void_p(slot_grad_ptr or None), C.c_void_p(ok_ptr or None)))
+
     # ---- per-instance vehicle and cost parameters (ltompc_set_instance_params, DESIGN.md §10) ----------------------------
     def set_theta(self, theta):
         """Per-instance values of the 16 parameters THETA_NAMES, from the next make_step / make_step_dev / rollout_dev / plant_step
@@ -752,6 +840,29 @@ def _table_values(values, n):
     return v
 
 
+def _table_sets(values, n):
+    """(n_sets, 4, n) float64 value rows of set_table_sets; shape and values are checked here, before any call."""
+    v = np.array(values, dtype=np.float64, order="C", copy=True)
+    if v.ndim != 3 or v.shape[0] < 1 or v.shape[1:] != (len(TABLE_ROW_NAMES), n):
+        raise ValueError(f"set_table_sets: values must have shape (n_sets >= 1, {len(TABLE_ROW_NAMES)}, {n}), got {v.shape}")
+    if not np.isfinite(v).all():
+        g, r, i = map(int, np.argwhere(~np.isfinite(v))[0])
+        raise ValueError(f"set_table_sets: non-finite value in set {g} ({TABLE_ROW_NAMES[r]}, knot {i})")
+    return v
+
+
+def _set_index(index, B, n_sets):
+    """(B,) int32 set of every instance; shape, type and range are checked here, before any call."""
+    ix = np.asarray(index)
+    if ix.shape != (B,) or ix.dtype.kind not in "iu":
+        raise ValueError(f"set_table_sets: index must be ({B},) integers, got shape {ix.shape}, dtype {ix.dtype}")
+    bad = (ix < 0) | (ix >= n_sets)
+    if bad.any():
+        b = int(np.argwhere(bad)[0][0])
+        raise ValueError(f"set_table_sets: index[{b}] = {int(ix[b])} is outside [0, {n_sets})")
+    return np.array(ix, dtype=np.int32, order="C", copy=True)
+
+
 class SplitMPC:
     """The batch as `n_parts` handles of batch / n_parts instances, each on its own HIP stream and driven by its own host thread
     (ctypes releases the GIL during a call).  Instances are independent NLPs, so the parts need not tick together: while one
@@ -956,6 +1067,66 @@ class SplitMPC:
     def table_values(self):
         """The value rows in effect (every part holds the same ones): those of the first part."""
         return self.parts[0].table_values()
+
+    @property
+    def n_table_sets(self):
+        return self.parts[0].n_table_sets
+
+    def set_table_sets(self, values=None, index=None):
+        """BatchedMPC.set_table_sets: the values go to every part, the index is split by rows (both checked first: a bad set
+        changes no part)."""
+        if values is None and index is None:
+            for p in self.parts:
+                p.set_table_sets(None, None)
+            return
+        n_sets = self.n_table_sets
+        if values is not None:
+            values = _table_sets(values, self.n_table)
+            n_sets = values.shape[0]
+        elif not n_sets:
+            raise ValueError("set_table_sets: values=None keeps the sets in effect, and there are none")
+        if index is not None:
+            index = _set_index(index, self.B, n_sets)
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.set_table_sets(values, None if index is None else index[lo:hi])
+
+    def set_table_sets_dev(self, n_sets: int, values_ptr: int = 0, index_ptr: int = 0):
+        """BatchedMPC.set_table_sets_dev on every part: each copies the same values and its rows of the (B,) int32 index on its
+        own stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.set_table_sets_dev(n_sets, values_ptr, index_ptr + 4 * lo if index_ptr else 0)
+
+    def table_sets(self):
+        """The sets in effect: the values of the first part (every part holds the same ones), the index stitched by rows."""
+        r = [p.table_sets() for p in self.parts]
+        return None if r[0] is None else (r[0][0], np.concatenate([q[1] for q in r]))
+
+    def adjoint_table_sets(self, gX=None, gU=None, slots: bool = False):
+        """BatchedMPC.adjoint_table_sets of every part with its rows of the cotangents: grad_sets summed over the parts in part
+        order (on the host), slot_grad and ok stitched in the caller's order."""
+        gX = None if gX is None else np.asarray(gX, dtype=np.float64)
+        gU = None if gU is None else np.asarray(gU, dtype=np.float64)
+        r = [p.adjoint_table_sets(None if gX is None else gX[lo:hi], None if gU is None else gU[lo:hi], slots)
+             for p, (lo, hi) in zip(self.parts, self.bounds)]
+        out = dict(r[0], ok=np.concatenate([q["ok"] for q in r]))
+        gs = r[0]["grad_sets"].copy()
+        for q in r[1:]:
+            gs += q["grad_sets"]
+        out["grad_sets"] = gs
+        if slots:
+            out["slot_grad"] = np.concatenate([q["slot_grad"] for q in r])
+        return out
+
+    def adjoint_table_sets_dev(self, gX_ptr: int, gU_ptr: int, grad_sets_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.adjoint_table_sets_dev with the same arrays, as adjoint_tables_dev: grad_sets (n_sets,4,n_table) summed over
+        the parts in part order (the first part overwrites, every later one adds after the part before it has finished)."""
+        N = self.N
+        for i, (p, (lo, hi)) in enumerate(zip(self.parts, self.bounds)):
+            if i and grad_sets_ptr:
+                self.parts[i - 1].synchronize()
+            p.adjoint_table_sets_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0, grad_sets_ptr,
+                                     slot_grad_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if slot_grad_ptr else 0,
+                                     ok_ptr + 4 * lo if ok_ptr else 0, add=i > 0)
 
     def sensitivities(self, trajectory: bool = False):
         """BatchedMPC.sensitivities of every part, stitched in the caller's order."""
