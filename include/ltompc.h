@@ -674,6 +674,39 @@ int ltompc_export_state_dev(ltompc_handle h, const int* idx_dev, int n, double* 
 int ltompc_import_state(ltompc_handle h, const int* idx, int n, const double* blob);
 int ltompc_import_state_dev(ltompc_handle h, const int* idx_dev, int n, const double* blob_dev);
 
+/* Solve records: differentiate any earlier solve of a handle.  The derivative passes (ltompc_get_sensitivities,
+ * ltompc_get_param_sensitivities, ltompc_get_adjoint, ltompc_get_adjoint_tables, ltompc_get_jvp and their _dev / _add_dev forms)
+ * read the handle's last solve in place, so the next solve, guess, reset, import or table set takes it away.  A record is a
+ * device copy of everything those passes read of one solve (about 83 N + 50 doubles per instance), in the caller's instance
+ * order; while one is selected the passes run on it instead of the live solve, on the same kernels.
+ *   ltompc_record_size     device bytes of one record of this handle.
+ *   ltompc_record_save     captures the solve the live passes would refer to now.  *rec == NULL: a record from the handle's free
+ *                          list, else a new one (allocates and synchronises once); *rec != NULL: that record is overwritten.  Reuse
+ *                          and overwrite only enqueue one gather kernel and two copies on the handle's stream.  Read-only on the
+ *                          handle, allowed inside an open loop.  Fails when there is no solve to differentiate, and on a handle
+ *                          with per-instance table sets in effect (records of such solves are out of scope).
+ *   ltompc_record_select   rec: the passes run on it from now on; NULL: back to the live solve.  A change of selection drops the
+ *                          cached factorisation and results: the first pass after it re-linearises and re-factorises (about one
+ *                          iteration).  Everything else - solves, plant steps, rollouts, setters, reset / import, the accessors of
+ *                          the iterate and the statistics - keeps working on the live handle and touches neither record nor
+ *                          selection.  Refused inside an open loop; ltompc_loop_begin / ltompc_loop_tick are refused while a record
+ *                          is selected.  A pass the recorded solve itself could not run (theta passes after a rollout, ...) is
+ *                          refused with the message of the live call.
+ *   ltompc_record_release  back to the handle's free list (deselects it first when selected).  Never frees device memory.
+ *   ltompc_record_trim     frees the records of the free list (synchronises).
+ *   ltompc_record_stats    records in use and on the free list; either output may be NULL.
+ * Whatever happens on the handle between save and select, a pass on a record returns the bits it would have returned right after
+ * the recorded solve (grad_tables: up to the order of its atomic adds, as on the live solve).  A record of another handle, a
+ * released or trimmed one is refused.  ltompc_destroy frees every record of the handle.
+ * Return 0 (ltompc_record_size: the size), or < 0 with ltompc_last_error(). */
+typedef struct ltompc_record_s* ltompc_record;
+long long ltompc_record_size(ltompc_handle h);
+int ltompc_record_save(ltompc_handle h, ltompc_record* rec);
+int ltompc_record_select(ltompc_handle h, ltompc_record rec);
+int ltompc_record_release(ltompc_handle h, ltompc_record rec);
+int ltompc_record_trim(ltompc_handle h);
+int ltompc_record_stats(ltompc_handle h, int* in_use, int* free_);
+
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:
  * index 0 eval (k_eval or k_eval8), 1 riccati (8 instances per wavefront), 2 expand (k_expand or k_expand8), 3 linesearch,

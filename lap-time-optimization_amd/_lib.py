@@ -114,6 +114,13 @@ def lib() -> C.CDLL:
         L.ltompc_export_state_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.ltompc_import_state.argtypes = [C.c_void_p, _ip, C.c_int, _dp]
         L.ltompc_import_state_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ltompc_record_size.argtypes = [C.c_void_p]
+        L.ltompc_record_size.restype = C.c_longlong
+        L.ltompc_record_save.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.ltompc_record_select.argtypes = [C.c_void_p, C.c_void_p]
+        L.ltompc_record_release.argtypes = [C.c_void_p, C.c_void_p]
+        L.ltompc_record_trim.argtypes = [C.c_void_p]
+        L.ltompc_record_stats.argtypes = [C.c_void_p, _ip, _ip]
         _lib = L
     return _lib
 

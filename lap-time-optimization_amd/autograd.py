@@ -12,10 +12,13 @@ device "cpu" runs the layer on CPU tensors).  Streams, simple and safe: torch's 
 is called and the handle after, so the layer neither overlaps with torch's work nor needs the handle on torch's stream.
 
 The handle is stateful: derivatives refer to ITS last solve.  mpc_solve records the handle's `solve_count`; backward / jvp raise
-a RuntimeError when another solve or initial guess has run on the handle since (solve, differentiate, then solve again; or use
-one handle per solve that is differentiated later).  Instances with ok = 0 give zero gradients, as the C interface does.
+a RuntimeError when another solve or initial guess has run on the handle since (solve, differentiate, then solve again), unless
+the solve was made with keep=True: it then carries a solve record (BatchedMPC.record) and is differentiated from that, at any
+later time, on the same handle.  Instances with ok = 0 give zero gradients, as the C interface does.
 """
 from __future__ import annotations
+
+import contextlib
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -52,9 +55,14 @@ def _fresh(mpc, count, what):
                            f"differentiated (solve_count {mpc.solve_count}, recorded {count}); its derivatives are gone")
 
 
+def _on(mpc, rec):
+    """the passes of the body on `rec` (selected on enter, deselected on exit whatever happens); None: on the live solve"""
+    return mpc.differentiating(rec) if rec is not None else contextlib.nullcontext()
+
+
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mpc, x0, u_prev, theta, tables):
+    def forward(ctx, mpc, x0, u_prev, theta, tables, keep=False):
         B, N = mpc.B, mpc.N
         _check(mpc, "mpc_solve: x0", x0, (B, NX))
         if tables is not None:
@@ -78,6 +86,7 @@ class _Solve(torch.autograd.Function):
         mpc.make_step_dev(x0.data_ptr(), u0.data_ptr())
         mpc.prediction_dev(X.data_ptr(), U.data_ptr())
         mpc.sensitivities_dev(0, ok.data_ptr())  # (ok, and the factorisation that backward / jvp share)
+        ctx.rec = mpc.record() if keep else None  # (keep: this solve's own record; released when the graph that holds ctx is freed)
         mpc.synchronize()
         ctx.mpc, ctx.count, ctx.has = mpc, mpc.solve_count, (u_prev is not None, theta is not None, tables is not None)
         ctx.mark_non_differentiable(ok)
@@ -87,7 +96,8 @@ class _Solve(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_u0, g_X, g_U, _g_ok):
         mpc = ctx.mpc
-        _fresh(mpc, ctx.count, "backward")
+        if ctx.rec is None:
+            _fresh(mpc, ctx.count, "backward")
         B, N = mpc.B, mpc.N
         gX = _dense(mpc, g_X, (B, N + 1, NX))
         gU = _dense(mpc, g_U, (B, N, NU)).clone()
@@ -99,19 +109,21 @@ class _Solve(torch.autograd.Function):
         want_tables = ctx.has[2] and ctx.needs_input_grad[4]
         gtab = _new(mpc, NROWS, mpc.n_table) if want_tables else None
         _sync_torch(mpc)
-        mpc.adjoint_dev(gX.data_ptr(), gU.data_ptr(), gp.data_ptr(), gth.data_ptr() if want_theta else 0, 0)
-        if want_tables:
-            mpc.adjoint_tables_dev(gX.data_ptr(), gU.data_ptr(), gtab.data_ptr(), 0, 0)
-        mpc.synchronize()
-        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth, gtab
+        with _on(mpc, ctx.rec):
+            mpc.adjoint_dev(gX.data_ptr(), gU.data_ptr(), gp.data_ptr(), gth.data_ptr() if want_theta else 0, 0)
+            if want_tables:
+                mpc.adjoint_tables_dev(gX.data_ptr(), gU.data_ptr(), gtab.data_ptr(), 0, 0)
+            mpc.synchronize()
+        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth, gtab, None
 
     @staticmethod
-    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta, t_tables):
+    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta, t_tables, _keep=None):
         mpc = ctx.mpc
         if t_tables is not None and ctx.has[2] and bool((t_tables != 0).any()):  # (torch hands zeros for an input without a tangent)
             raise RuntimeError("mpc_solve jvp: forward mode is not available for `tables` (there is no directional pass in the "
                                "tables; use reverse mode, which returns grad_tables)")
-        _fresh(mpc, ctx.count, "jvp")
+        if ctx.rec is None:
+            _fresh(mpc, ctx.count, "jvp")
         B, N = mpc.B, mpc.N
         if not ctx.has[0]:
             t_uprev = None
@@ -125,8 +137,9 @@ class _Solve(torch.autograd.Function):
         if dp is None and dth is None:
             return _dense(mpc, None, (B, NU)), tX.zero_(), tU.zero_(), None
         _sync_torch(mpc)
-        mpc.jvp_dev(dp.data_ptr() if dp is not None else 0, dth.data_ptr() if dth is not None else 0, tX.data_ptr(), tU.data_ptr(), 0)
-        mpc.synchronize()
+        with _on(mpc, ctx.rec):
+            mpc.jvp_dev(dp.data_ptr() if dp is not None else 0, dth.data_ptr() if dth is not None else 0, tX.data_ptr(), tU.data_ptr(), 0)
+            mpc.synchronize()
         return tU[:, 0].clone(), tX, tU, None
 
 
@@ -179,7 +192,7 @@ class _Plant(torch.autograd.Function):
         return out
 
 
-def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None):
+def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None, keep=False):
     """One solve of the handle as a differentiable function: (u0 (B,2), X (B,N+1,8), U (B,N,2), ok (B,) int32) of x0 (B,8),
     u_prev (B,2; None: the one the handle makes itself, no gradient), theta (B,16 per-instance rows in THETA_NAMES order;
     None: the rows or params in effect, no gradient) and tables ((4, n_table): the value rows kappa, n_left, n_right, v_ref
@@ -192,9 +205,17 @@ def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None):
     raises a RuntimeError (there is no directional pass in the tables).  ok is not differentiable; where it is 0 all
     derivatives are 0.  Torch's current stream is synchronised before the calls and the handle after them.
 
+    keep=True: the forward saves a solve record (BatchedMPC.record) and keeps it with the graph.  backward and
+    forward mode then run on that record (select, the passes, deselect) whatever the handle has done since - later solves,
+    other theta rows, other tables (the record has its own copies of the four rows) - so a T-tick closed loop backpropagates
+    on ONE handle; solve_count is not checked.  The record goes back to the handle's free list when the graph is freed, so
+    a training loop allocates T records once.  keep=False (the default) is the code path described above.
+
     The tables set here stay on the handle: they are the CONTROLLER's belief of the track from then on, and the handle's plant
     step reads the kappa row too (plant_step below takes no tables and has no gradient w.r.t. them)."""
-    return _Solve.apply(mpc, x0, u_prev, theta, tables)
+    if not keep:
+        return _Solve.apply(mpc, x0, u_prev, theta, tables)
+    return _Solve.apply(mpc, x0, u_prev, theta, tables, True)
 
 
 def plant_step(mpc, x, u, theta=None, n_sub=400):

@@ -4,7 +4,61 @@
 // Part of ltompc.hip's translation unit, after ltompc_solver and its helpers; the passes' state is ltompc_solver::dv (DerivState).
 #pragma once
 
+// Solve records.  SolveView: the fields of the handle through which the passes below address "the solve".  A record
+// holds one that points into its own buffers; while an entry point runs on a selected record the two are exchanged (RecScope), so
+// the drivers below are the same code on the same kernels either way.  The passes' buffers (QP, RC, RS, LS, the PV / AJ / JV / TJ
+// planes, the results) stay the handle's.
+struct SolveView {
+  Consts K;
+  Consts* d_K = nullptr;
+  Work W{}, *d_W = nullptr, Ws{}, *d_Ws = nullptr;
+  WorkPI Wpi{}, *d_Wpi = nullptr, Wspi{}, *d_Wspi = nullptr;
+  double* d_psens_uprev = nullptr;
+  bool pi_solve = false, ts_solve = false, ref_eval = false, eval8 = true;
+  int n_sets = 0;
+  Sens sens = Sens::no_solve;  // ... and how far the passes have got on it (DerivState)
+  Psens psens = Psens::none;
+  bool fact = false, pv_valid = false, kept_uprev = false;
+};
+struct ltompc_record_s {
+  bool in_use = false;  // else on the handle's free list
+  char* base = nullptr;  // the one device buffer, and the arrays in it
+  double *X = nullptr, *C = nullptr, *U = nullptr, *L1 = nullptr, *L2 = nullptr, *T = nullptr, *NU = nullptr, *st = nullptr, *x0 = nullptr,
+         *uprev = nullptr, *TH = nullptr, *tab = nullptr;
+  int* si = nullptr;
+  SolveView v;
+};
+
 namespace {
+
+int ws_alloc(ltompc_solver* h);  // (warm_state_host.h)
+const int* ws_inverse(ltompc_solver* h);
+
+void view_exchange(ltompc_solver* h, SolveView& v) {
+  DerivState& D = h->dv;
+  std::swap(h->K, v.K), std::swap(h->d_K, v.d_K), std::swap(h->W, v.W), std::swap(h->d_W, v.d_W), std::swap(D.Ws, v.Ws), std::swap(D.d_Ws, v.d_Ws);
+  std::swap(h->Wpi, v.Wpi), std::swap(h->d_Wpi, v.d_Wpi), std::swap(D.Wspi, v.Wspi), std::swap(D.d_Wspi, v.d_Wspi);
+  std::swap(D.d_psens_uprev, v.d_psens_uprev), std::swap(h->pi_solve, v.pi_solve), std::swap(h->ts_solve, v.ts_solve);
+  std::swap(h->ref_eval, v.ref_eval), std::swap(h->eval8, v.eval8), std::swap(h->n_sets, v.n_sets);
+  std::swap(D.sens, v.sens), std::swap(D.psens, v.psens), std::swap(D.fact, v.fact), std::swap(D.pv_valid, v.pv_valid);
+  std::swap(D.kept_uprev, v.kept_uprev);
+}
+// For the duration of a derivative entry point: the selected record in the handle's place (nothing when none is selected).
+struct RecScope {
+  ltompc_solver* h;
+  explicit RecScope(ltompc_solver* h_) : h(h_) {
+    if (h->rec_sel) view_exchange(h, h->rec_sel->v);
+  }
+  ~RecScope() {
+    if (h->rec_sel) view_exchange(h, h->rec_sel->v);
+  }
+  RecScope(const RecScope&) = delete;
+  RecScope& operator=(const RecScope&) = delete;
+};
+int no_record(ltompc_solver* h, const char* who) {
+  if (h->rec_sel) return fail(std::string(who) + ": not available while a solve record is selected (ltompc_record_select(h, NULL) first)");
+  return 0;
+}
 
 constexpr hipMemcpyKind D2H = hipMemcpyDeviceToHost, D2D = hipMemcpyDeviceToDevice;
 
@@ -39,12 +93,10 @@ void sens_factorise(ltompc_solver* h) {
   D.fact = true;
 }
 
-// The sensitivity pass of the last solve (sensitivity.h), enqueued on the handle's stream: linearisation and head-less sweep
-// when not done since that solve (or when the instances have moved since), the forward pass for du0 / ok / margin, and the
-// trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
-int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
+// The buffers of the (x0, u_prev) pass, which every pass shares, on the first request (one synchronisation).  On the live handle
+// only: a record brings a Ws of its own that points at them.
+int sens_buffers(ltompc_solver* h) {
   DerivState& D = h->dv;
-  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess, set_table_values and set_table_sets discard the last solve)");
   const int B = h->B, N = h->N, Bp = h->Bp;
   if (!D.d_Ws) {
     Work& Ws = D.Ws = h->W;
@@ -60,6 +112,17 @@ int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
     HIPCHECK(hipStreamSynchronize(h->stream));
     if (h->d_th_solve && sync_pi_work(h)) return -1;
   }
+  return 0;
+}
+
+// The sensitivity pass of the last solve (sensitivity.h), enqueued on the handle's stream: linearisation and head-less sweep
+// when not done since that solve (or when the instances have moved since), the forward pass for du0 / ok / margin, and the
+// trajectories when asked for.  Results in the caller's order, cached until the next solve or initial guess.
+int sens_compute(ltompc_solver* h, const bool traj, const char* who) {
+  DerivState& D = h->dv;
+  if (D.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess, set_table_values and set_table_sets discard the last solve)");
+  const int B = h->B, N = h->N, Bp = h->Bp;
+  if (sens_buffers(h)) return -1;
   if (D.sens == Sens::solved) {
     sens_factorise(h);
     hipLaunchKernelGGL(k_sens_forward, dim3(Bp / 8), dim3(64), 0, h->stream, D.Ws, (const int*)D.d_sens_inertia, h->K.bd.ni, D.d_sens_du0,
@@ -283,12 +346,211 @@ int planes_to_rows(ltompc_solver* h, const double* planes, const int f0, const i
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------ solve records
+// The arrays of a record inside its one device buffer, each 256-byte aligned, in bytes from the start; `end`: the size.
+struct RecLayout {
+  size_t X, C, U, L1, L2, T, NU, st, x0, uprev, pup, TH, tab, si, orig, K, W, Ws, Wpi, Wspi, end;
+};
+RecLayout rec_layout(const ltompc_solver* h) {
+  const size_t N = h->N, Bp = h->Bp, ni = h->K.bd.ni, nel = h->K.bd.nel, D = sizeof(double);
+  RecLayout L{};
+  size_t at = 0;
+  const auto take = [&](size_t& field, const size_t bytes) { field = at, at += (bytes + 255) / 256 * 256; };
+  take(L.X, 8 * (N + 1) * Bp * D), take(L.C, 8 * N * Bp * D), take(L.U, 2 * N * Bp * D), take(L.L1, 8 * N * Bp * D), take(L.L2, 8 * N * Bp * D);
+  take(L.T, (ni + NNL + nel) * N * Bp * D), take(L.NU, ni * N * Bp * D), take(L.st, (size_t)ST_NF * Bp * D), take(L.x0, 8 * Bp * D);
+  take(L.uprev, 2 * Bp * D), take(L.pup, 2 * Bp * D), take(L.TH, (size_t)LTOMPC_NTHETA * Bp * D);
+  take(L.tab, (size_t)LTOMPC_TABLE_VALUE_ROWS * h->n_table * D), take(L.si, (size_t)SI_NF * Bp * sizeof(int)), take(L.orig, Bp * sizeof(int));
+  take(L.K, sizeof(Consts)), take(L.W, sizeof(Work)), take(L.Ws, sizeof(Work)), take(L.Wpi, sizeof(WorkPI)), take(L.Wspi, sizeof(WorkPI));
+  L.end = at;
+  return L;
+}
+
+ltompc_record_s* rec_find(ltompc_solver* h, const ltompc_record_s* rec) {
+  for (ltompc_record_s* r : h->recs)
+    if (r == rec) return r;
+  return nullptr;
+}
+int rec_check(ltompc_solver* h, const ltompc_record_s* rec, const char* who) {
+  const ltompc_record_s* r = rec_find(h, rec);
+  if (!r) return fail(std::string(who) + ": not a record of this handle (one of another handle, or freed by ltompc_record_trim)");
+  if (!r->in_use) return fail(std::string(who) + ": the record has been released (ltompc_record_release)");
+  return 0;
+}
+
+// A new record: its buffer, the Work / Consts copies that point into it, here and on the device (one synchronisation).  The
+// pointers never change afterwards, so a record that is reused or overwritten uploads nothing.
+int rec_create(ltompc_solver* h, ltompc_record_s** out) {
+  if (sens_buffers(h)) return -1;  // (QP, RC, RS, LS and the zeroed si of the record's Ws are the handle's)
+  const RecLayout L = rec_layout(h);
+  ltompc_record_s* r = new ltompc_record_s;
+  if (h->dalloc(&r->base, L.end)) {
+    delete r;
+    return -1;
+  }
+  char* const p = r->base;
+  const auto dbl = [&](const size_t at) { return reinterpret_cast<double*>(p + at); };
+  r->X = dbl(L.X), r->C = dbl(L.C), r->U = dbl(L.U), r->L1 = dbl(L.L1), r->L2 = dbl(L.L2), r->T = dbl(L.T), r->NU = dbl(L.NU), r->st = dbl(L.st);
+  r->x0 = dbl(L.x0), r->uprev = dbl(L.uprev), r->TH = dbl(L.TH), r->tab = dbl(L.tab), r->si = reinterpret_cast<int*>(p + L.si);
+  SolveView& v = r->v;
+  v.d_psens_uprev = dbl(L.pup);
+  v.K = h->K;  // (grids, g0_*, inv_*, period, params, options and the bounds pattern are the handle's and immutable; the value rows the record's)
+  using tp = gptr<const double>;
+  const size_t n = h->n_table;
+  v.K.T.kappa = (tp)r->tab, v.K.T.n_left = (tp)(r->tab + n), v.K.T.n_right = (tp)(r->tab + 2 * n), v.K.T.v_ref = (tp)(r->tab + 3 * n);
+  Work& W = v.W = h->W;
+  using dp = gptr<double>;
+  W.X = (dp)r->X, W.C = (dp)r->C, W.U = (dp)r->U, W.L1 = (dp)r->L1, W.L2 = (dp)r->L2, W.T = (dp)r->T, W.NU = (dp)r->NU, W.st = (dp)r->st;
+  W.x0 = (dp)r->x0, W.uprev = (dp)r->uprev, W.si = (gptr<int>)r->si, W.orig = (gptr<const int>)reinterpret_cast<int*>(p + L.orig);
+  Work& Ws = v.Ws = W;
+  const Work& hs = h->dv.Ws;
+  Ws.QP = hs.QP, Ws.RC = hs.RC, Ws.RS = hs.RS, Ws.LS = hs.LS, Ws.si = hs.si;
+  static_cast<Work&>(v.Wpi) = W, v.Wpi.TH = (tp)r->TH;
+  static_cast<Work&>(v.Wspi) = Ws, v.Wspi.TH = (tp)r->TH;
+  v.d_K = reinterpret_cast<Consts*>(p + L.K), v.d_W = reinterpret_cast<Work*>(p + L.W), v.d_Ws = reinterpret_cast<Work*>(p + L.Ws);
+  v.d_Wpi = reinterpret_cast<WorkPI*>(p + L.Wpi), v.d_Wspi = reinterpret_cast<WorkPI*>(p + L.Wspi);
+  std::vector<int> ident(h->Bp);
+  for (int b = 0; b < h->Bp; b++) ident[b] = b;
+  hipError_t e = hipMemcpyAsync(p + L.orig, ident.data(), sizeof(int) * h->Bp, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(v.d_K, &v.K, sizeof(Consts), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(v.d_W, &v.W, sizeof(Work), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(v.d_Ws, &v.Ws, sizeof(Work), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(v.d_Wpi, &v.Wpi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(v.d_Wspi, &v.Wspi, sizeof(WorkPI), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    h->dfree(r->base);
+    delete r;
+    return fail(std::string("ltompc_record_save: upload of the record's constants failed: ") + hipGetErrorString(e));
+  }
+  h->recs.push_back(r);
+  *out = r;
+  return 0;
+}
+
+// The gather of the solve that the live passes would refer to now into r (enqueued only), and its flags.
+int rec_fill(ltompc_solver* h, ltompc_record_s* r) {
+  const int N = h->N, Bp = h->Bp, ni = h->K.bd.ni, nel = h->K.bd.nel;
+  const Work& W = h->W;
+  RecPlanes P{};
+  const auto add = [&](const void* src, void* dst, const int rows, const int flags) {
+    P.p[P.n++] = RecPlane{(gptr<const void>)src, (gptr<void>)dst, rows, flags}, P.rows += rows;
+  };
+  add((const double*)W.NU, r->NU, ni * N, 0), add((const double*)W.T, r->T, (ni + NNL + nel) * N, 0), add((const double*)W.X, r->X, 8 * (N + 1), 0);
+  add((const double*)W.C, r->C, 8 * N, 0), add((const double*)W.L1, r->L1, 8 * N, 0), add((const double*)W.L2, r->L2, 8 * N, 0);
+  add((const double*)W.U, r->U, 2 * N, 0), add((const double*)W.st, r->st, ST_NF, 0), add((const double*)W.x0, r->x0, 8, 0);
+  add((const double*)W.uprev, r->uprev, 2, 0);
+  for (const int f : {SI_STATUS, SI_NODE0, SI_REINIT})  // (the words d_sens_riccati8 looks at; the other rows stay zero)
+    add((const int*)W.si + (size_t)f * Bp, r->si + (size_t)f * Bp, 1, REC_W32);
+  add(h->dv.d_psens_uprev, r->v.d_psens_uprev, 2, REC_DIRECT);  // (B x 2 in the caller's order: 2 Bp words as they are)
+  if (h->pi_solve) add(h->d_th_solve, r->TH, LTOMPC_NTHETA, REC_DIRECT);
+  static_assert(15 <= REC_MAX_PLANES, "k_rec_save's descriptor table");
+  const int* inv = nullptr;
+  if (h->packed) {
+    if (ws_alloc(h)) return -1;
+    inv = ws_inverse(h);
+  }
+  hipLaunchKernelGGL(k_rec_save, dim3((Bp + 255) / 256, (P.rows + REC_ROWS - 1) / REC_ROWS), dim3(256), 0, h->stream, P, inv, h->B, Bp);
+  HIPCHECK(hipGetLastError());
+  const size_t n = h->n_table, D = sizeof(double);  // value rows: kappa; n_left, n_right, v_ref (rows 1; 3, 4, 5 of d_tables)
+  HIPCHECK(hipMemcpyAsync(r->tab, h->d_tables + n, n * D, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(r->tab + n, h->d_tables + 3 * n, 3 * n * D, hipMemcpyDeviceToDevice, h->stream));
+  SolveView& v = r->v;
+  v.pi_solve = h->pi_solve, v.ts_solve = false, v.n_sets = 0, v.ref_eval = h->ref_eval, v.eval8 = h->eval8, v.kept_uprev = h->dv.kept_uprev;
+  v.sens = Sens::solved, v.psens = Psens::none, v.fact = v.pv_valid = false;
+  return 0;
+}
+
+// A change of selection: what the passes have cached (the factorisation, the PV planes, the results) belongs to the solve they ran on last.
+void rec_invalidate(Sens& sens, Psens& psens, bool& fact, bool& pv_valid) {
+  if (sens != Sens::no_solve) sens = Sens::solved;
+  psens = Psens::none, fact = pv_valid = false;
+}
+void rec_set_selection(ltompc_solver* h, ltompc_record_s* rec) {
+  if (h->rec_sel == rec) return;
+  DerivState& D = h->dv;
+  rec_invalidate(D.sens, D.psens, D.fact, D.pv_valid);
+  if (rec) rec_invalidate(rec->v.sens, rec->v.psens, rec->v.fact, rec->v.pv_valid);
+  h->rec_sel = rec;
+}
+
 }  // namespace
 
 extern "C" {
 
+long long ltompc_record_size(ltompc_handle h) {
+  if (!h) return fail("null handle");
+  return (long long)rec_layout(h).end;
+}
+
+int ltompc_record_save(ltompc_handle h, ltompc_record* rec) {
+  const char* who = "ltompc_record_save";
+  if (!h) return fail("null handle");
+  if (!rec) return fail(std::string(who) + ": null argument");
+  if (*rec && rec_check(h, *rec, who)) return -1;
+  if (h->dv.sens == Sens::no_solve) return fail(std::string(who) + ": no solve to differentiate (make_step, make_step_dev or rollout_dev first; set_initial_guess, set_table_values and set_table_sets discard the last solve)");
+  if (h->n_sets || h->ts_solve)
+    return fail(std::string(who) + ": records of solves with per-instance table sets are out of scope (ltompc_set_table_sets; n_sets = 0 and a new solve bring them back)");
+  HIPCHECK(hipSetDevice(h->device));
+  ltompc_record_s* r = *rec;
+  if (!r) {
+    for (ltompc_record_s* f : h->recs)
+      if (!f->in_use) r = f;
+    if (!r && rec_create(h, &r)) return -1;
+  }
+  if (rec_fill(h, r)) return -1;
+  r->in_use = true;
+  *rec = r;
+  return 0;
+}
+
+int ltompc_record_select(ltompc_handle h, ltompc_record rec) {
+  const char* who = "ltompc_record_select";
+  if (!h) return fail("null handle");
+  if (h->dv.loop_mode) return fail(std::string(who) + ": not available inside an open loop (ltompc_loop_end first)");
+  if (rec && rec_check(h, rec, who)) return -1;
+  rec_set_selection(h, rec);
+  return 0;
+}
+
+int ltompc_record_release(ltompc_handle h, ltompc_record rec) {
+  const char* who = "ltompc_record_release";
+  if (!h) return fail("null handle");
+  if (!rec) return fail(std::string(who) + ": null argument");
+  if (rec_check(h, rec, who)) return -1;
+  if (h->rec_sel == rec) rec_set_selection(h, nullptr);
+  rec->in_use = false;
+  return 0;
+}
+
+int ltompc_record_trim(ltompc_handle h) {
+  if (!h) return fail("null handle");
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipStreamSynchronize(h->stream));  // (nothing in flight reads a buffer when it goes)
+  std::vector<ltompc_record_s*> kept;
+  for (ltompc_record_s* r : h->recs) {
+    if (r->in_use) {
+      kept.push_back(r);
+      continue;
+    }
+    h->dfree(r->base);
+    delete r;
+  }
+  h->recs.swap(kept);
+  return 0;
+}
+
+int ltompc_record_stats(ltompc_handle h, int* in_use, int* free_) {
+  if (!h) return fail("null handle");
+  int n_use = 0;
+  for (const ltompc_record_s* r : h->recs) n_use += r->in_use ? 1 : 0;
+  if (in_use) *in_use = n_use;
+  if (free_) *free_ = (int)h->recs.size() - n_use;
+  return 0;
+}
+
 int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, double* dU_dp, int* ok, double* margin) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (sens_compute(h, dX_dp || dU_dp, "ltompc_get_sensitivities")) return -1;
   const DerivState& D = h->dv;
@@ -303,6 +565,7 @@ int ltompc_get_sensitivities(ltompc_handle h, double* du0_dp, double* dX_dp, dou
 
 int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (sens_compute(h, false, "ltompc_sensitivities_dev")) return -1;
   if (copy_out(h, D2D, du0_dp_dev, h->dv.d_sens_du0, (size_t)2 * SENS_NP * h->B)) return -1;
@@ -311,6 +574,7 @@ int ltompc_sensitivities_dev(ltompc_handle h, double* du0_dp_dev, int* ok_dev) {
 
 int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_dth, double* dU_dth, int* ok) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (psens_compute(h, dX_dth || dU_dth, "ltompc_get_param_sensitivities")) return -1;
   const DerivState& D = h->dv;
@@ -324,6 +588,7 @@ int ltompc_get_param_sensitivities(ltompc_handle h, double* du0_dth, double* dX_
 
 int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (psens_compute(h, false, "ltompc_param_sensitivities_dev")) return -1;
   if (copy_out(h, D2D, du0_dth_dev, h->dv.d_psens_du0, (size_t)2 * PS_NT * h->B)) return -1;
@@ -332,6 +597,7 @@ int ltompc_param_sensitivities_dev(ltompc_handle h, double* du0_dth_dev, int* ok
 
 int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_p_dev, double* grad_theta_dev, int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (adj_compute(h, gX_dev, gU_dev, grad_theta_dev != nullptr, "ltompc_adjoint_dev")) return -1;
   if (copy_out(h, D2D, grad_p_dev, h->dv.d_adj_gp, (size_t)ADJ_NP * h->B)) return -1;
@@ -342,6 +608,7 @@ int ltompc_adjoint_dev(ltompc_handle h, const double* gX_dev, const double* gU_d
 int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, double* grad_p, double* grad_theta, int* ok) {
   const char* who = "ltompc_get_adjoint";
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
   const size_t B = h->B, N = h->N;
   for (size_t b = 0; b < B; b++) {
@@ -367,6 +634,7 @@ int ltompc_get_adjoint(ltompc_handle h, const double* gX, const double* gU, doub
 int ltompc_adjoint_tables_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_tables_dev, double* slot_grad_dev,
                               int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_tables_dev")) return -1;
   if (copy_out(h, D2D, grad_tables_dev, h->dv.d_tab_gt, (size_t)TAB_ROWS * h->n_table)) return -1;
@@ -377,6 +645,7 @@ int ltompc_adjoint_tables_dev(ltompc_handle h, const double* gX_dev, const doubl
 int ltompc_adjoint_tables_add_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_tables_dev, double* slot_grad_dev,
                                   int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_tables_add_dev")) return -1;
   if (grad_tables_dev) {
@@ -391,6 +660,7 @@ int ltompc_adjoint_tables_add_dev(ltompc_handle h, const double* gX_dev, const d
 int ltompc_get_adjoint_tables(ltompc_handle h, const double* gX, const double* gU, double* grad_tables, double* slot_grad, int* ok) {
   const char* who = "ltompc_get_adjoint_tables";
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
   const size_t B = h->B, N = h->N;
   for (size_t b = 0; b < B; b++) {
@@ -418,6 +688,7 @@ int ltompc_get_adjoint_tables(ltompc_handle h, const double* gX, const double* g
 int ltompc_adjoint_table_sets_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_sets_dev, double* slot_grad_dev,
                                   int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_table_sets_dev", true)) return -1;
   if (copy_out(h, D2D, grad_sets_dev, h->dv.d_tab_gs, (size_t)TAB_ROWS * h->n_table * h->n_sets)) return -1;
@@ -428,6 +699,7 @@ int ltompc_adjoint_table_sets_dev(ltompc_handle h, const double* gX_dev, const d
 int ltompc_adjoint_table_sets_add_dev(ltompc_handle h, const double* gX_dev, const double* gU_dev, double* grad_sets_dev, double* slot_grad_dev,
                                       int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (tab_compute(h, gX_dev, gU_dev, "ltompc_adjoint_table_sets_add_dev", true)) return -1;
   if (grad_sets_dev) {
@@ -442,6 +714,7 @@ int ltompc_adjoint_table_sets_add_dev(ltompc_handle h, const double* gX_dev, con
 int ltompc_get_adjoint_table_sets(ltompc_handle h, const double* gX, const double* gU, double* grad_sets, double* slot_grad, int* ok) {
   const char* who = "ltompc_get_adjoint_table_sets";
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   if (!gX && !gU) return fail(std::string(who) + ": gX and gU are both NULL (no cotangent)");
   const size_t B = h->B, N = h->N;
   for (size_t b = 0; b < B; b++) {
@@ -466,6 +739,7 @@ int ltompc_get_adjoint_table_sets(ltompc_handle h, const double* gX, const doubl
 
 int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_dev, double* tX_dev, double* tU_dev, int* ok_dev) {
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   HIPCHECK(hipSetDevice(h->device));
   if (jvp_compute(h, dp_dev, dtheta_dev, tX_dev, tU_dev, "ltompc_jvp_dev")) return -1;
   return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
@@ -474,6 +748,7 @@ int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_d
 int ltompc_get_jvp(ltompc_handle h, const double* dp, const double* dtheta, double* tX, double* tU, int* ok) {
   const char* who = "ltompc_get_jvp";
   if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
   if (!dp && !dtheta) return fail(std::string(who) + ": dp and dtheta are both NULL (no direction)");
   const size_t B = h->B, N = h->N;
   for (size_t b = 0; b < B; b++) {
@@ -537,7 +812,7 @@ int ltompc_loop_begin(ltompc_handle h, int mode) {
   const char* who = "ltompc_loop_begin";
   if (!h) return fail("null handle");
   if (mode < 1 || mode > 3) return fail(std::string(who) + ": mode must be 1 (theta enters the controller), 2 (the plant) or 3 (both)");
-  if (no_table_sets(h, who, "the closed-loop sensitivities are")) return -1;
+  if (no_record(h, who) || no_table_sets(h, who, "the closed-loop sensitivities are")) return -1;
   if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
   if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
   HIPCHECK(hipSetDevice(h->device));
@@ -555,6 +830,7 @@ int ltompc_loop_tick_dev(ltompc_handle h, const double* x_dev, const double* u0_
   if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
   if (!h || !x_dev || !u0_dev || !x_next_dev) return fail(std::string(who) + ": null argument");
   DerivState& D = h->dv;
+  if (no_record(h, who)) return -1;
   if (!D.loop_mode) return fail(std::string(who) + ": no loop (ltompc_loop_begin first)");
   if (no_table_sets(h, who, "the closed-loop sensitivities are")) return -1;
   HIPCHECK(hipSetDevice(h->device));

@@ -40,6 +40,8 @@
 //                 start of a solve with a per-instance cold flag), k_ws_reset_* (ltompc_reset_instances), k_ws_guess (ltompc_set_guess),
 //                 k_ws_export / k_ws_import (the carried state of chosen instances <-> instance-major blobs, an LDS tile transpose)
 //   warm_state_host.h (host, part of ltompc.hip only) their C entry points
+//   record.h      k_rec_save: everything the derivative passes read of a solve, gathered into a record in the caller's order
+//                 (ltompc_record_save); the passes then run on a Work that points into the record
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
@@ -65,3 +67,4 @@
 #include "plant_sensitivity.h"
 #include "table_sensitivity.h"
 #include "warm_state.h"
+#include "record.h"

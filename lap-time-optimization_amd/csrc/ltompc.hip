@@ -77,6 +77,8 @@ struct DerivState {
   int tab_gs_cap = 0;
 };
 
+struct ltompc_record_s;  // a solve record (deriv_passes.h)
+
 struct ltompc_solver {
   Consts K;
   Work W;
@@ -167,6 +169,10 @@ struct ltompc_solver {
   bool ts_narrow = true;   // the narrow _ts Riccati kernels got their LDS limit (as pi_narrow)
   WorkTS Wts{};
   WorkTS* d_Wts = nullptr;
+  // solve records (ltompc_record_*): every record of the handle, in use or on its free list, and the one the
+  // derivative passes run on (nullptr: the live solve).  Nothing of this exists on a handle that never saved one.
+  std::vector<ltompc_record_s*> recs;
+  ltompc_record_s* rec_sel = nullptr;
 
   // (P may be a gptr<T>: a global-address-space pointer in the device pass of the compiler, a plain one on the host)
   // work = true: an array that the kernels fill before they read it.  LTOMPC_POISON=1 (debug) fills those with 0xFF bytes
@@ -739,7 +745,8 @@ int ltompc_destroy(ltompc_handle h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : h->allocs) (void)hipFree(p);
+  for (void* p : h->allocs) (void)hipFree(p);  // (the records' buffers among them)
+  for (ltompc_record_s* r : h->recs) delete r;
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->h_active) (void)hipHostFree(h->h_active);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);

@@ -12,6 +12,34 @@ from .tables import TrackTables
 KERNEL_CLASSES = ("eval", "riccati", "expand", "linesearch", "pick", "update", "riccati1", "step1")  # include/ltompc.h
 
 
+class SolveRecord:
+    """One saved solve of a BatchedMPC (BatchedMPC.record), or one per part of a SplitMPC (`parts`).  release() hands it back to
+    the handle's free list: idempotent, and a no-op once the handle is closed (ltompc_destroy frees its records)."""
+
+    def __init__(self, mpc, rec=None, parts=None):
+        self._mpc, self._rec, self.parts, self._released = mpc, rec, parts, False
+
+    @property
+    def released(self) -> bool:
+        return self._released
+
+    def release(self):
+        if self._released:
+            return
+        self._released = True
+        if self.parts is not None:
+            for r in self.parts:
+                r.release()
+        elif getattr(self._mpc, "_h", None) is not None and self._mpc._h.value:
+            check(lib().ltompc_record_release(self._mpc._h, self._rec))
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
 class BatchedMPC:
     """B receding-horizon NLPs of the reference's controller (src/mpc/controller.py:9-103), solved on the GPU.
 
@@ -212,6 +240,59 @@ class BatchedMPC:
         instances): enqueued on the handle's stream, NOT checked."""
         check(lib().ltompc_import_state_dev(self._h, C.c_void_p(idx_ptr or None), int(n), C.c_void_p(blob_ptr)))
         self._instances_changed()
+
+    # ---- solve records (ltompc_record_*, DESIGN.md §17) -------------------------------------------
+    def record(self, into: "SolveRecord | None" = None) -> "SolveRecord":
+        """A device copy of everything the derivative passes read of the last solve (the one they would refer to now), so that
+        they can run on it after the handle has gone on: select_record / differentiating.  into: a record of this handle to
+        overwrite.  From the handle's free list when it has one, else allocated (one synchronisation); reuse and overwrite only
+        enqueue.  Read-only on the handle (solve_count stays).  Release it (SolveRecord.release, or drop it) when done."""
+        if into is not None and (into._mpc is not self or into._released):
+            raise ValueError("record(into=): a live record of this handle, or None")
+        rec = C.c_void_p(into._rec.value) if into is not None else C.c_void_p()
+        check(lib().ltompc_record_save(self._h, C.byref(rec)))
+        return into if into is not None else SolveRecord(self, rec)
+
+    def select_record(self, rec: "SolveRecord | None"):
+        """The derivative passes (sensitivities, param_sensitivities, adjoint, adjoint_tables, jvp and their _dev forms) run on
+        `rec` from now on, bit for bit as right after the recorded solve; None: back to the live solve.  Everything else keeps
+        working on the live handle.  The first pass after a change re-linearises and re-factorises (about one iteration)."""
+        if rec is not None and (not isinstance(rec, SolveRecord) or rec._mpc is not self):
+            raise ValueError("select_record: a record of this handle, or None")
+        if rec is not None and rec._released:
+            raise ValueError("select_record: the record has been released")
+        check(lib().ltompc_record_select(self._h, rec._rec if rec is not None else None))
+
+    def differentiating(self, rec: "SolveRecord"):
+        """Context manager: select_record(rec) on enter, select_record(None) on exit, whatever the body does."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            self.select_record(rec)
+            try:
+                yield rec
+            finally:
+                self.select_record(None)
+        return scope()
+
+    @property
+    def record_size(self) -> int:
+        """Device bytes of one record of this handle."""
+        n = lib().ltompc_record_size(self._h)
+        if n < 0:
+            check(-1)
+        return int(n)
+
+    def trim_records(self):
+        """Free the device memory of the released records (synchronises)."""
+        check(lib().ltompc_record_trim(self._h))
+
+    def record_stats(self):
+        """(records in use, records on the free list)."""
+        a, b = C.c_int(), C.c_int()
+        check(lib().ltompc_record_stats(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     # ---- parametric sensitivities (ltompc_get_sensitivities, DESIGN.md §9) -----------------------
     def sensitivities(self, trajectory: bool = False):
@@ -1127,6 +1208,37 @@ class SplitMPC:
             p.adjoint_table_sets_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0, grad_sets_ptr,
                                      slot_grad_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if slot_grad_ptr else 0,
                                      ok_ptr + 4 * lo if ok_ptr else 0, add=i > 0)
+
+    # ---- solve records: one record per part (BatchedMPC.record)
+    def record(self, into: SolveRecord | None = None) -> SolveRecord:
+        if into is not None and (into._mpc is not self or into._released):
+            raise ValueError("record(into=): a live record of this handle, or None")
+        if into is not None:
+            for p, r in zip(self.parts, into.parts):
+                p.record(into=r)
+            return into
+        return SolveRecord(self, parts=[p.record() for p in self.parts])
+
+    def select_record(self, rec: SolveRecord | None):
+        if rec is not None and (not isinstance(rec, SolveRecord) or rec._mpc is not self or rec._released):
+            raise ValueError("select_record: a live record of this handle, or None")
+        for i, p in enumerate(self.parts):
+            p.select_record(rec.parts[i] if rec is not None else None)
+
+    def differentiating(self, rec: SolveRecord):
+        return BatchedMPC.differentiating(self, rec)
+
+    @property
+    def record_size(self) -> int:
+        return sum(p.record_size for p in self.parts)
+
+    def trim_records(self):
+        for p in self.parts:
+            p.trim_records()
+
+    def record_stats(self):
+        s = [p.record_stats() for p in self.parts]
+        return sum(a for a, _ in s), sum(b for _, b in s)
 
     def sensitivities(self, trajectory: bool = False):
         """BatchedMPC.sensitivities of every part, stitched in the caller's order."""
