@@ -766,6 +766,11 @@ int ltompc_test_model(ltompc_handle h, int n, double eps, const double* x, const
                       double* J, double* H, double* cval, double* cgrad, double* cH, double* gval,
                       double* ggrad, double* gH);
 
+/* Test hook: the five table look-ups of a horizon slot at n arc lengths: kappa at s[t]; kappa, v_ref, n_left, n_right at
+ * s[n - 1 - t]; value, slope and second derivative each (n x 5 x 3).  `direct`: one look-up after the other, as the plant and the
+ * derivative passes do; `batched`: fetched in one batch and finished afterwards, as the evaluation kernels do.  Equal bit for bit. */
+int ltompc_test_lut(ltompc_handle h, int n, double eps, const double* s, double* direct, double* batched);
+
 /* Test hook: the friction-ellipse constraints (front, rear; params.ell_*) at n points: val n x 2, grad n x 2 x 8, H n x 2 x 8 x 8. */
 int ltompc_test_ellipse(ltompc_handle h, int n, const double* x, double* val, double* grad, double* H);
 

@@ -434,6 +434,32 @@ __global__ void k_test_model(Consts K, int n, double eps, const double* __restri
 }
 
 
+// test hook: the five table look-ups of a slot, kappa at sc = s[t], kappa / v_ref / n_left / n_right at sx = s[n - 1 - t] (value, slope,
+// second derivative each: 15 numbers), once look-up by look-up through lut_eval (`direct`) and once through the batched halves
+// slot_luts_fetch / _pin / _finish (`batched`).  The two must agree bit for bit.
+__device__ __forceinline__ void test_lut_point(const Tables& T, const double eps, const double sc, const double sx, double* direct,
+                                               double* batched) {
+  lut_eval(T.s_kappa, T.kappa, T.n, T.g0_kappa, T.inv_kappa, T.period, sc, eps, direct[0], direct[1], direct[2]);
+  lut_eval(T.s_kappa, T.kappa, T.n, T.g0_kappa, T.inv_kappa, T.period, sx, eps, direct[3], direct[4], direct[5]);
+  lut_eval(T.s_arc, T.v_ref, T.n, T.g0_arc, T.inv_arc, T.period, sx, eps, direct[6], direct[7], direct[8]);
+  lut_eval(T.s_arc, T.n_left, T.n, T.g0_arc, T.inv_arc, T.period, sx, eps, direct[9], direct[10], direct[11]);
+  lut_eval(T.s_arc, T.n_right, T.n, T.g0_arc, T.inv_arc, T.period, sx, eps, direct[12], direct[13], direct[14]);
+  SlotLutsRaw R;
+  SlotLuts L;
+  slot_luts_fetch(T, sc, sx, R);
+  slot_luts_pin(R);
+  slot_luts_finish(T, R, eps, true, true, L);
+  const Lut3 l[5] = {L.kc, L.kx, L.vr, L.nl, L.nr};
+  for (int q = 0; q < 5; q++) batched[3 * q] = l[q].v, batched[3 * q + 1] = l[q].d1, batched[3 * q + 2] = l[q].d2;
+}
+__global__ void k_test_lut(Consts K, int n, double eps, const double* __restrict__ s, double* __restrict__ direct, double* __restrict__ batched) {
+  int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  double d[15], c[15];
+  test_lut_point(K.T, eps, s[t], s[n - 1 - t], d, c);
+  for (int q = 0; q < 15; q++) direct[(size_t)t * 15 + q] = d[q], batched[(size_t)t * 15 + q] = c[q];
+}
+
 // test hook: friction-ellipse constraints at given points: val n x 2, grad n x 2 x 8, H n x 2 x 8 x 8 (full state indexing)
 __global__ void k_test_ellipse(Consts K, int n, const double* __restrict__ x, double* __restrict__ val, double* __restrict__ grad, double* __restrict__ H) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;

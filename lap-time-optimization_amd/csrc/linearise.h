@@ -177,6 +177,7 @@ struct Slot {
 template <bool WITH_DUAL, class BP, bool ELL, bool PI = false, bool TS = false>
 __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, int k, int b, double eps, Slot& S) {
   const int N = W.N;
+  constexpr bool LUT_ONE = WITH_DUAL, LUT_POINT = !WITH_DUAL && !TS;  // (how the table look-ups are batched, below)
   const double hdt = K.o.t_step, rho = W.st[(size_t)ST_RHO * W.Bp + b];
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -190,13 +191,38 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
   for (int i = 0; i < 8; i++) l1[i] = PL(W.L1, i, k, N), l2[i] = PL(W.L2, i, k, N);
 #pragma unroll
   for (int i = 0; i < 36; i++) S.Hc[i] = 0.0, S.Hxp[i] = 0.0;
+  const bool nl_early = (k + 1 <= N - 1);
+  // the five table look-ups of the slot in one batch of loads (model.h: slot_luts_fetch), ahead of the evaluations that use them.
+  // LUT_POINT (k_expand, whose registers do not hold the finished look-ups of x_{k+1} across the evaluation at c_k): one batch
+  // per point.  Neither (k_expand_ts, which holds the set's pointers as well and spilled with either): look-up by look-up.
+  SlotLutsRaw lraw;
+  SlotLuts lut;
+  if constexpr (LUT_ONE) {
+    const Tables& Tb = inst_tables<TS>(K.T, W, b);
+    slot_luts_fetch(Tb, S.c[0], S.xp[0], lraw);
+    slot_luts_pin(lraw);
+    slot_luts_finish(Tb, lraw, eps, k != N - 1, nl_early, lut);
+  } else if constexpr (LUT_POINT) {
+    const Tables& Tb = inst_tables<TS>(K.T, W, b);
+    slot_luts_fetch_c(Tb, S.c[0], lraw);
+    slot_luts_pin_c(lraw);
+    slot_luts_finish_c(Tb, lraw, eps, lut);
+  }
   double f1[8], f2[8], J[48];
-  rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.c, f1, J, l1, hdt, S.Hc);
+  if constexpr (LUT_ONE || LUT_POINT) rhs_derivs(inst_params<PI>(K.p, W, b), lut.kc, S.c, f1, J, l1, hdt, S.Hc);
+  else rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.c, f1, J, l1, hdt, S.Hc);
 #pragma unroll
   for (int i = 0; i < 64; i++) S.E1[i] = 0.0, S.E2[i] = 0.0;
 #pragma unroll
   for (int i = 0; i < 48; i++) S.E1[i] = hdt * J[i];
-  rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.xp, f2, J, l2, hdt, S.Hxp);
+  if constexpr (LUT_POINT) {
+    const Tables& Tb = inst_tables<TS>(K.T, W, b);
+    slot_luts_fetch_x(Tb, S.xp[0], lraw);
+    slot_luts_pin_x(lraw);
+    slot_luts_finish_x(Tb, lraw, eps, k != N - 1, nl_early, lut);
+  }
+  if constexpr (LUT_ONE || LUT_POINT) rhs_derivs(inst_params<PI>(K.p, W, b), lut.kx, S.xp, f2, J, l2, hdt, S.Hxp);
+  else rhs_derivs(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.xp, f2, J, l2, hdt, S.Hxp);
 #pragma unroll
   for (int i = 0; i < 48; i++) S.E2[i] = hdt * J[i];
   f1[6] = f2[6] = S.u[0], f1[7] = f2[7] = S.u[1];
@@ -208,7 +234,8 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
   }
 #pragma unroll
   for (int i = 0; i < 8; i++) S.gcost[i] = 0.0, S.gc0[i] = 0.0, S.gc1[i] = 0.0, S.gxp1[i] = 0.0, S.dcd[i] = 0.0;
-  S.cost = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.xp, k == N - 1, S.gcost, S.Hxp);
+  if constexpr (LUT_ONE || LUT_POINT) S.cost = cost_eval(inst_params<PI>(K.p, W, b), lut.vr, S.xp, k == N - 1, S.gcost, S.Hxp);
+  else S.cost = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, S.xp, k == N - 1, S.gcost, S.Hxp);
 #pragma unroll
   for (int i = 0; i < 8; i++) S.gxp0[i] = S.gcost[i], S.dxd[i] = S.gcost[i];
   S.Du[0] = S.Du[1] = 0.0, S.gub0[0] = S.gub0[1] = 0.0, S.gub1[0] = S.gub1[1] = 0.0, S.dud[0] = S.dud[1] = 0.0;
@@ -253,7 +280,8 @@ __device__ __forceinline__ void linearise_slot(const Consts& K, const Work& W, i
     asm volatile("" : "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(nq[0]), "+v"(nq[1]), "+v"(nq[2]), "+v"(eq[0]), "+v"(eq[1]), "+v"(eq[2]));
 #endif
     double hss[3], hmm[3];
-    cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, S.xp, S.gv, S.gs, S.gn, S.gm, hss, hmm);
+    if constexpr (LUT_ONE || LUT_POINT) cons_eval(K.p, lut.nl, lut.nr, S.xp, S.gv, S.gs, S.gn, S.gm, hss, hmm);
+    else cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, S.xp, S.gv, S.gs, S.gn, S.gm, hss, hmm);
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       int mm = m_nl + q;

@@ -50,35 +50,77 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
     for (int i = 0; i < 8; i++) txk[i] = xk[i] + alpha * dxk[i], txp[i] = xp[i] + alpha * dxp[i], tc[i] = c[i] + alpha * dc[i];
 #pragma unroll
     for (int i = 0; i < 2; i++) tu[i] = u[i] + alpha * du[i], tv[i] = v[i] + alpha * dv[i];
+    // the five table look-ups of the candidate (kappa at both points, v_ref / n_left / n_right at x_{k+1}) in ONE batch of
+    // loads, and with them the slacks of the track constraints (and their elastic variables): loaded unconditionally, used
+    // conditionally.  (Looked up one after the other inside rhs_val / cost_eval / cons_eval, and the slacks pair by pair between
+    // the tests of nl and rho, these were eleven dependent round trips.)
+    const Tables& Tb = inst_tables<TS>(K.T, W, b);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (!PIN) {
+      // (k_step1: the candidate's point complete before the knots are asked for.  Left alone the compiler fetches the two arc
+      //  lengths first and issues the knots among the other 50 loads of the state: state and step, the knots and the slacks
+      //  together do not fit the 256 registers of two wavefronts per SIMD)
+      asm volatile("" : "+v"(tc[0]), "+v"(tc[1]), "+v"(tc[2]), "+v"(tc[3]), "+v"(tc[4]), "+v"(tc[5]), "+v"(tc[6]), "+v"(tc[7]),
+                        "+v"(txp[0]), "+v"(txp[1]), "+v"(txp[2]), "+v"(txp[3]), "+v"(txp[4]), "+v"(txp[5]), "+v"(txp[6]), "+v"(txp[7]),
+                        "+v"(txk[0]), "+v"(txk[1]), "+v"(txk[2]), "+v"(txk[3]), "+v"(txk[4]), "+v"(txk[5]), "+v"(txk[6]), "+v"(txk[7]),
+                        "+v"(tu[0]), "+v"(tu[1]), "+v"(tv[0]), "+v"(tv[1]));
+    }
+#endif
+    SlotLutsRaw lraw;
+    slot_luts_fetch(Tb, tc[0], txp[0], lraw);
+    constexpr int NTR = ELL ? 5 : 3;
+    double tn[NTR], dtn[NTR], en[NTR], den[NTR];
+    const auto fetch_track = [&](const int m0) {  // (these planes exist for every slot: k_expand writes zeros in the last one)
+#pragma unroll
+      for (int q = 0; q < NTR; q++) {
+        tn[q] = PL(W.T, m0 + q, k, N), dtn[q] = PL(W.dT, m0 + q, k, N);
+        en[q] = PL(W.T, K.bd.ni + q, k, N), den[q] = PL(W.dT, K.bd.ni + q, k, N);
+      }
+    };
+    // compile-time bound pattern: the slacks of the simple bounds in one batch of loads as well.  PIN: in the batch of the knots
+    // (k_linesearch); else on their own after the cost (k_step1, two wavefronts per SIMD: 80 registers more in the batch of the
+    // knots and it spills)
+    double t0[BP::fixed ? MAX_NI : 1] = {}, d0[BP::fixed ? MAX_NI : 1] = {};  // (zero: the pinning below touches whole chunks of 8)
+    const auto fetch_bounds = [&] { for_each_bound<BP>(K.p, [&](int mm, int, int, double, double) { t0[mm] = PL(W.T, mm, k, N), d0[mm] = PL(W.dT, mm, k, N); }); };
+    const int nb = BP::fixed ? for_each_bound<BP>(K.p, [](int, int, int, double, double) {}) : 0;
+    if (BP::fixed && PIN) fetch_bounds();
+    if (BP::fixed) fetch_track(nb);
+    // (the knots were issued first: the look-ups are finished while the slacks are still on their way)
+    slot_luts_pin(lraw);
+    SlotLuts lut;
+    slot_luts_finish(Tb, lraw, eps, k != N - 1, nl, lut);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (BP::fixed) {
+      // (all of them in registers before the first use: left alone the compiler issues and awaits them pair by pair)
+#pragma unroll
+      for (int q = 0; q < MAX_NI; q += 8)
+        if (PIN && q < nb) {
+          double* a = t0 + q;
+          double* c = d0 + q;
+          asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
+                            "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]));
+        }
+#pragma unroll
+      for (int q = 0; q < NTR; q++) asm volatile("" : "+v"(tn[q]), "+v"(dtn[q]), "+v"(en[q]), "+v"(den[q]));
+    }
+#endif
     double f1[8], f2[8];
-    rhs_val(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, tc, tu, f1);
-    rhs_val(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, txp, tu, f2);
+    rhs_val(inst_params<PI>(K.p, W, b), lut.kc.v, tc, tu, f1);
+    rhs_val(inst_params<PI>(K.p, W, b), lut.kx.v, txp, tu, f2);
     double th = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       th += fabs(hdt * f1[i] + 2.0 * txk[i] - 1.5 * tc[i] - 0.5 * txp[i]);
       th += fabs(hdt * f2[i] - 2.0 * txk[i] + 4.5 * tc[i] - 2.5 * txp[i]);
     }
-    double co = cost_eval(inst_params<PI>(K.p, W, b), inst_tables<TS>(K.T, W, b), eps, txp, k == N - 1, nullptr, nullptr);
+    double co = cost_eval(inst_params<PI>(K.p, W, b), lut.vr, txp, k == N - 1, nullptr, nullptr);
 #pragma unroll
     for (int i = 0; i < 2; i++) co += inst_r_du<PI>(K.p, W, b, i) * (tu[i] - tv[i]) * (tu[i] - tv[i]);
     // sum of log t as the log of products of 8 slacks (same grouping in linearise_slot): 3 logarithms instead of 23
     double sl = 0.0, pr = 1.0;
-    double tt[BP::fixed ? MAX_NI : 1];  // compile-time bound pattern: the slacks of the candidate in one batch of loads
+    double tt[BP::fixed ? MAX_NI : 1];
     if (BP::fixed) {
-      double t0[MAX_NI] = {}, d0[MAX_NI] = {};  // (zero: the pinning below touches whole chunks of 8)
-      const int nb = for_each_bound<BP>(K.p, [&](int mm, int, int, double, double) { t0[mm] = PL(W.T, mm, k, N), d0[mm] = PL(W.dT, mm, k, N); });
-      // (all of them in registers before the first use: left alone the compiler issues and awaits them pair by pair)
-#pragma unroll
-      for (int q = 0; q < MAX_NI; q += 8)
-        if (PIN && q < nb) {  // (k_step1, two wavefronts per SIMD, is faster without: fewer registers)
-#if defined(__HIP_DEVICE_COMPILE__)
-          double* a = t0 + q;
-          double* c = d0 + q;
-          asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
-                            "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]));
-#endif
-        }
+      if (!PIN) fetch_bounds();
 #pragma unroll
       for (int q = 0; q < MAX_NI; q++)
         if (q < nb) tt[q] = t0[q] + alpha * d0[q];
@@ -89,16 +131,17 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
       th += fabs(sg * (xv - val) + t), pr *= t;
       if ((mm & 7) == 7) sl += log(pr), pr = 1.0;
     });
+    if (!BP::fixed) fetch_track(m);  // run-time bound pattern: m is known only now
     if (nl) {
       double gv[3];
-      cons_eval(K.p, inst_tables<TS>(K.T, W, b), eps, txp, gv, nullptr, nullptr, nullptr, nullptr, nullptr);
+      cons_eval(K.p, lut.nl, lut.nr, txp, gv, nullptr, nullptr, nullptr, nullptr, nullptr);
 #pragma unroll
       for (int q = 0; q < 3; q++) {
-        double t = PL(W.T, m + q, k, N) + alpha * PL(W.dT, m + q, k, N);
+        double t = tn[q] + alpha * dtn[q];
         double e = 0.0;
         pr *= t;
         if (rho > 0.0) {  // elastic variable of the softened constraint: g - e + t = 0, cost rho e
-          e = PL(W.T, K.bd.ni + q, k, N) + alpha * PL(W.dT, K.bd.ni + q, k, N);
+          e = en[q] + alpha * den[q];
           pr *= e, co += rho * e;
         }
         th += fabs(gv[q] - e + t);
@@ -109,9 +152,9 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
         ellipse_val(K.p, txp, ge);
 #pragma unroll
         for (int q = 0; q < 2; q++) {
-          const int mm = m + 3 + q, me = K.bd.ni + 3 + q;
-          const double t = PL(W.T, mm, k, N) + alpha * PL(W.dT, mm, k, N);
-          const double e = PL(W.T, me, k, N) + alpha * PL(W.dT, me, k, N);
+          const int mm = m + 3 + q;
+          const double t = tn[NTR - 2 + q] + alpha * dtn[NTR - 2 + q];
+          const double e = en[NTR - 2 + q] + alpha * den[NTR - 2 + q];
           pr *= t, pr *= e, co += K.p.ell_penalty * e;
           th += fabs(ge[q] - e + t);
           if ((mm & 7) == 7) sl += log(pr), pr = 1.0;

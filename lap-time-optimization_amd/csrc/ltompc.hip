@@ -1536,6 +1536,24 @@ int ltompc_test_model(ltompc_handle h, int n, double eps, const double* x, const
   return 0;
 }
 
+// Test hook: the five table look-ups of a slot at n arc lengths (host arrays), kappa at s[t], kappa / v_ref / n_left / n_right at
+// s[n - 1 - t]: value, slope, second derivative each (n x 15), through lut_eval (direct) and through the batched halves (batched).
+int ltompc_test_lut(ltompc_handle h, int n, double eps, const double* s, double* direct, double* batched) {
+  if (!h || n < 1 || !s || !direct || !batched) return fail("ltompc_test_lut: bad argument");
+  HIPCHECK(hipSetDevice(h->device));
+  double *ds, *dd, *db;
+  HIPCHECK(hipMalloc((void**)&ds, sizeof(double) * n));
+  HIPCHECK(hipMalloc((void**)&dd, sizeof(double) * 15 * n));
+  HIPCHECK(hipMalloc((void**)&db, sizeof(double) * 15 * n));
+  HIPCHECK(hipMemcpy(ds, s, sizeof(double) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_test_lut, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->K, n, eps, ds, dd, db);
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  HIPCHECK(hipMemcpy(direct, dd, sizeof(double) * 15 * n, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(batched, db, sizeof(double) * 15 * n, hipMemcpyDeviceToHost));
+  (void)hipFree(ds), (void)hipFree(dd), (void)hipFree(db);
+  return 0;
+}
+
 // Test hook: friction-ellipse constraints (front, rear) at n points (host arrays): val n x 2, grad n x 2 x 8, H n x 2 x 64.
 int ltompc_test_ellipse(ltompc_handle h, int n, const double* x, double* val, double* grad, double* H) {
   if (!h || n < 1 || !x || !val || !grad || !H) return fail("ltompc_test_ellipse: bad argument");

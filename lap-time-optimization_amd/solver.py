@@ -819,6 +819,15 @@ class BatchedMPC:
                                       *(dptr(out[k]) for k in ("f", "J", "H", "cval", "cgrad", "cH", "gval", "ggrad", "gH"))))
         return out
 
+    def test_lut(self, s, eps: float = 0.0):
+        """The five table look-ups of a slot (kappa at s[t]; kappa, v_ref, n_left, n_right at s[n - 1 - t]; value, slope, second
+        derivative each) through lut_eval and through the batched halves: two (n, 5, 3) arrays."""
+        s = np.ascontiguousarray(np.asarray(s, float).ravel())
+        n = s.shape[0]
+        direct, batched = np.empty((n, 5, 3)), np.empty((n, 5, 3))
+        check(lib().ltompc_test_lut(self._h, n, C.c_double(eps), dptr(s), dptr(direct), dptr(batched)))
+        return direct, batched
+
     def test_ellipse(self, x):
         x = np.ascontiguousarray(np.asarray(x, float).reshape(-1, NX))
         n = x.shape[0]
