@@ -145,6 +145,14 @@ __global__ void k_shift(Work W, int pass) {
 }
 
 
+// ------------------------------------------------------------------------------------------ the host loop's poll
+// The two counters the host reads every poll_every passes, written by one thread into pinned host memory through its device
+// address (`out`), instead of two 4-byte device-to-host copies, each a copy kernel of its own on the stream.  The host reads
+// them after the stream synchronisation that follows.
+__global__ void __launch_bounds__(64) k_poll(const int* __restrict__ n_active, const int* __restrict__ ls_last, int* __restrict__ out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = n_active[0], out[1] = ls_last[0];
+}
+
 // ------------------------------------------------------------------------------------------ compaction
 __global__ void k_act_identity(int* act, int* nact, int B) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;

@@ -584,6 +584,131 @@ __global__ void __launch_bounds__(64) k_update(const Consts* __restrict__ Kp, co
   d_update(K, W, k, la.act[j]);
 }
 
+// ------------------------------------------------------------------------------------------ the update of k_step1, split
+// d_update as k_step1 runs it is one wavefront's work: N lanes, a whole slot each, a dozen dependent round trips while 280 lanes
+// idle - and before it d_pick, 8 lanes.  None of the update's operands depends on d_pick (which writes W.st, W.si, W.filt and
+// ls_list only), so wavefronts 1..4 fetch them WHILE d_pick runs (d_update_fetch) and after the barrier only the seven state
+// words are a round trip away (d_update_store).  Lane w = tid - 64 owns row r = w & 7 of the slots (w >> 3) + 32 j: the pairs
+// (x_r, dx_r) of node k + 1, (c_r, dc_r), (l1_r, n1_r), (l2_r, n2_r), (u_r, du_r) for r < 2, the elastic pair (e_r, de_r) for
+// r < 3 + nel, and the inequality units (t_m, dt_m, nu_m, dn_m), m = r + 8 q - whole units, every word formed by d_update's own
+// statement.  Within a slot the loads are unconditional with clamped indices (d_update's idiom), the conditions apply to the stores.
+constexpr int UPD_ROUNDS = 2;  // rounds of 32 slots held across the pick: N <= 64 (N = 40 entirely); later slots are loaded after it
+constexpr int UPD_QUADS = 3;   // inequality units of a row held with them: ni <= 24 (the reference's bound pattern: at most 23)
+struct UpdRow {
+  double a[5], d[5], e, de;                                              // x, c, l1, l2, u and their steps / trial values; elastic
+  double t[UPD_QUADS], dt[UPD_QUADS], nu[UPD_QUADS], dn[UPD_QUADS];      // inequalities m0 + r + 8 q
+};
+struct UpdRegs {
+  UpdRow row[UPD_ROUNDS];
+};
+
+__device__ __forceinline__ void upd_load_pairs(const Consts& K, const Work& W, const int k, const int r, const int b, UpdRow& v) {
+  const int N = W.N, ni = K.bd.ni, nel = K.bd.nel;
+  const int ru = r < 2 ? r : 1, re = ni + (r < 3 + nel ? r : 0);  // (rows without such a unit repeat another's word: branch-free loads)
+  v.a[0] = PL(W.X, r, k + 1, N + 1), v.d[0] = PL(W.dX, r, k + 1, N + 1), v.a[1] = PL(W.C, r, k, N), v.d[1] = PL(W.dC, r, k, N);
+  v.a[2] = PL(W.L1, r, k, N), v.d[2] = PL(W.nL1, r, k, N), v.a[3] = PL(W.L2, r, k, N), v.d[3] = PL(W.nL2, r, k, N);
+  v.a[4] = PL(W.U, ru, k, N), v.d[4] = PL(W.dU, ru, k, N);
+  v.e = PL(W.T, re, k, N), v.de = PL(W.dT, re, k, N);
+}
+__device__ __forceinline__ void upd_load_quads(const Consts& K, const Work& W, const int k, const int r, const int b, const int m0, UpdRow& v) {
+  const int N = W.N, ni = K.bd.ni, nel = K.bd.nel, nact = (k + 1 <= N - 1) ? ni : ni - 3 - nel;  // (the last slot has no nonlinear constraints)
+  const int last = nact > 0 ? nact - 1 : 0;
+#pragma unroll
+  for (int q = 0; q < UPD_QUADS; q++) {
+    const int m = m0 + r + 8 * q < nact ? m0 + r + 8 * q : last;
+    v.t[q] = PL(W.T, m, k, N), v.dt[q] = PL(W.dT, m, k, N), v.nu[q] = PL(W.NU, m, k, N), v.dn[q] = PL(W.dNU, m, k, N);
+  }
+}
+__device__ __forceinline__ void upd_store_pairs(const Consts& K, const Work& W, const int k, const int r, const int b, const double alpha,
+                                                const double rho, const UpdRow& v) {
+  const int N = W.N, ni = K.bd.ni, nel = K.bd.nel;
+  PL(W.X, r, k + 1, N + 1) = v.a[0] + alpha * v.d[0];
+  PL(W.C, r, k, N) = v.a[1] + alpha * v.d[1];
+  PL(W.L1, r, k, N) = v.a[2] + alpha * (v.d[2] - v.a[2]);
+  PL(W.L2, r, k, N) = v.a[3] + alpha * (v.d[3] - v.a[3]);
+  if (r < 2) PL(W.U, r, k, N) = v.a[4] + alpha * v.d[4];
+  // elastic variables (of the track constraints with rho > 0, of the friction ellipse with nel), not in the last slot
+  if (k + 1 <= N - 1 && (r < 3 ? rho > 0.0 : r < 3 + nel)) PL(W.T, ni + r, k, N) = v.e + alpha * v.de;
+}
+__device__ __forceinline__ void upd_store_quads(const Consts& K, const Work& W, const int k, const int r, const int b, const int m0,
+                                                const double alpha, const double a_dua, const double mu, const UpdRow& v) {
+  const int N = W.N, ni = K.bd.ni, nel = K.bd.nel, nact = (k + 1 <= N - 1) ? ni : ni - 3 - nel;
+#pragma unroll
+  for (int q = 0; q < UPD_QUADS; q++)
+    if (m0 + r + 8 * q < nact) {
+      const double tn = v.t[q] + alpha * v.dt[q];
+      const double nn = v.nu[q] + a_dua * v.dn[q];
+      const double lo = mu / (1e10 * tn), hi = 1e10 * mu / tn;  // IPOPT eq. (16)
+      PL(W.T, m0 + r + 8 * q, k, N) = tn, PL(W.NU, m0 + r + 8 * q, k, N) = nn < lo ? lo : (nn > hi ? hi : nn);
+    }
+}
+
+// wavefronts 1..4, beside d_pick: the operands of the first UPD_ROUNDS * 32 slots, one batch
+__device__ __forceinline__ void d_update_fetch(const Consts& K, const Work& W, const int tid, const int b, UpdRegs& R) {
+  const int N = W.N, w = tid - 64;
+#pragma unroll
+  for (int j = 0; j < UPD_ROUNDS; j++) {
+    // (a round past the horizon is skipped, not clamped: at N = 40 that is the second round of wavefronts 2..4, whole wavefronts,
+    //  and their 4600 repeated loads made the fetch longer than the pick it runs beside - the workgroup's loads go through one
+    //  cache port, a 64-byte sector per lane and load)
+    const int k = 32 * j + (w >> 3);
+    if (k < N) upd_load_pairs(K, W, k, w & 7, b, R.row[j]), upd_load_quads(K, W, k, w & 7, b, 0, R.row[j]);
+  }
+#if defined(__HIP_DEVICE_COMPILE__)
+  // in registers HERE, while the pick runs: not sunk to the stores behind the barrier
+#pragma unroll
+  for (int j = 0; j < UPD_ROUNDS; j++) {
+    UpdRow& v = R.row[j];
+    asm volatile("" : "+v"(v.a[0]), "+v"(v.d[0]), "+v"(v.a[1]), "+v"(v.d[1]), "+v"(v.a[2]), "+v"(v.d[2]), "+v"(v.a[3]), "+v"(v.d[3]),
+                 "+v"(v.a[4]), "+v"(v.d[4]), "+v"(v.e), "+v"(v.de));
+    asm volatile("" : "+v"(v.t[0]), "+v"(v.dt[0]), "+v"(v.nu[0]), "+v"(v.dn[0]), "+v"(v.t[1]), "+v"(v.dt[1]), "+v"(v.nu[1]), "+v"(v.dn[1]),
+                 "+v"(v.t[2]), "+v"(v.dt[2]), "+v"(v.nu[2]), "+v"(v.dn[2]));
+  }
+#endif
+}
+
+// all wavefronts, after the pick: the state it left, one round trip, then the stores
+__device__ __forceinline__ void d_update_store(const Consts& K, const Work& W, const int tid, const int b, const UpdRegs& R) {
+  const int N = W.N;
+  int shift = W.si[(size_t)SI_SHIFT * W.Bp + b], done = W.si[(size_t)SI_DONE * W.Bp + b], step = W.si[(size_t)SI_STEP * W.Bp + b];
+  double alpha = W.st[(size_t)ST_ALPHA * W.Bp + b], a_dua = W.st[(size_t)ST_ADUA * W.Bp + b];
+  double mu = W.st[(size_t)ST_MU * W.Bp + b], rho = W.st[(size_t)ST_RHO * W.Bp + b];
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(shift), "+v"(done), "+v"(step), "+v"(alpha), "+v"(a_dua), "+v"(mu), "+v"(rho));
+#endif
+  if (shift && !done) {  // options.resto_shift_retry, rare: the point comes from the backup planes (d_update)
+    for (int kk = tid; kk < N; kk += 320) {
+#if defined(__clang__)
+      // (the flags as d_update reads them next: its other branch is not compiled in a second time)
+      __builtin_assume(W.si[(size_t)SI_SHIFT * W.Bp + b] && !W.si[(size_t)SI_DONE * W.Bp + b]);
+#endif
+      d_update(K, W, kk, b);
+    }
+    return;
+  }
+  if (!step || done || tid < 64) return;
+  const int w = tid - 64, r = w & 7;
+#pragma unroll
+  for (int j = 0; j < UPD_ROUNDS; j++) {
+    const int k = 32 * j + (w >> 3);
+    if (k < N) upd_store_pairs(K, W, k, r, b, alpha, rho, R.row[j]), upd_store_quads(K, W, k, r, b, 0, alpha, a_dua, mu, R.row[j]);
+  }
+  // what was not held: slots from UPD_ROUNDS * 32 on, inequalities from UPD_QUADS * 8 on - load a batch, then store it
+  const int ni = K.bd.ni;
+  if (N <= UPD_ROUNDS * 32 && ni <= UPD_QUADS * 8) return;
+  for (int k = w >> 3; k < N; k += 32) {
+    UpdRow v;
+    if (k >= UPD_ROUNDS * 32) {
+      upd_load_pairs(K, W, k, r, b, v), upd_load_quads(K, W, k, r, b, 0, v);
+      upd_store_pairs(K, W, k, r, b, alpha, rho, v), upd_store_quads(K, W, k, r, b, 0, alpha, a_dua, mu, v);
+    }
+    for (int m0 = UPD_QUADS * 8; m0 < ni; m0 += UPD_QUADS * 8) {
+      upd_load_quads(K, W, k, r, b, m0, v);
+      upd_store_quads(K, W, k, r, b, m0, alpha, a_dua, mu, v);
+    }
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------ k_step1
 // Narrow launches: the whole step selection of ONE instance per workgroup (both line-search phases, the filter test
@@ -609,10 +734,15 @@ __global__ void __launch_bounds__(320) k_step1(const Consts* __restrict__ Kp, co
   STOCK(9);
   // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
   //  measures of all candidates exist already: one pass, same decisions)
-  if (tid < 64 && (tid & 7) == 0) d_pick(K, W, b, tid >> 3, 1, false);
+  // ... on 8 lanes of wavefront 0; the other wavefronts fetch the operands of the update meanwhile (d_update_fetch: nothing of
+  // them is held across the pick by wavefront 0, whose batch of loads needs the registers)
+  UpdRegs upd;
+  if (tid < 64) {
+    if ((tid & 7) == 0) d_pick(K, W, b, tid >> 3, 1, false);
+  } else d_update_fetch(K, W, tid, b, upd);
   __syncthreads();
   STOCK(10);
-  for (int kk = tid; kk < N; kk += 320) d_update(K, W, kk, b);
+  d_update_store(K, W, tid, b, upd);
   STOCK(11);
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK
@@ -641,10 +771,15 @@ __global__ void __launch_bounds__(320) k_step1_pi(const Consts* __restrict__ Kp,
   STOCK(9);
   // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
   //  measures of all candidates exist already: one pass, same decisions)
-  if (tid < 64 && (tid & 7) == 0) d_pick<true>(K, W, b, tid >> 3, 1, false);
+  // ... on 8 lanes of wavefront 0; the other wavefronts fetch the operands of the update meanwhile (d_update_fetch: nothing of
+  // them is held across the pick by wavefront 0, whose batch of loads needs the registers)
+  UpdRegs upd;
+  if (tid < 64) {
+    if ((tid & 7) == 0) d_pick<true>(K, W, b, tid >> 3, 1, false);
+  } else d_update_fetch(K, W, tid, b, upd);
   __syncthreads();
   STOCK(10);
-  for (int kk = tid; kk < N; kk += 320) d_update(K, W, kk, b);
+  d_update_store(K, W, tid, b, upd);
   STOCK(11);
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK
@@ -672,10 +807,15 @@ __global__ void __launch_bounds__(320) k_step1_ts(const Consts* __restrict__ Kp,
   STOCK(9);
   // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
   //  measures of all candidates exist already: one pass, same decisions)
-  if (tid < 64 && (tid & 7) == 0) d_pick<true, true>(K, W, b, tid >> 3, 1, false);
+  // ... on 8 lanes of wavefront 0; the other wavefronts fetch the operands of the update meanwhile (d_update_fetch: nothing of
+  // them is held across the pick by wavefront 0, whose batch of loads needs the registers)
+  UpdRegs upd;
+  if (tid < 64) {
+    if ((tid & 7) == 0) d_pick<true, true>(K, W, b, tid >> 3, 1, false);
+  } else d_update_fetch(K, W, tid, b, upd);
   __syncthreads();
   STOCK(10);
-  for (int kk = tid; kk < N; kk += 320) d_update(K, W, kk, b);
+  d_update_store(K, W, tid, b, upd);
   STOCK(11);
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK

@@ -90,6 +90,7 @@ struct ltompc_solver {
   double* d_u0_rm = nullptr;   // staging, row-major B x 2
   double* d_io = nullptr;      // staging for plant / slip forces
   int* h_active = nullptr;     // pinned
+  int* h_active_dev = nullptr; // ... its device address (k_poll writes the polled counters through it)
   int *d_act[2] = {nullptr, nullptr}, *d_nact[2] = {nullptr, nullptr};  // ping-pong lists of unfinished instances
   int last_compactions = 0;
   int *d_perm = nullptr, *d_orig = nullptr;  // packing: permutation of the current re-packing, original index of every physical slot
@@ -710,7 +711,8 @@ int ltompc_create(const ltompc_params* params, const ltompc_options* options, co
     ltompc_destroy(h);
     return -1;
   }
-  if (hipHostMalloc((void**)&h->h_active, sizeof(int) * 4) != hipSuccess) {
+  if (hipHostMalloc((void**)&h->h_active, sizeof(int) * 4) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&h->h_active_dev, h->h_active, 0) != hipSuccess) {
     ltompc_destroy(h);
     return fail("hipHostMalloc failed");
   }
@@ -1021,8 +1023,7 @@ int ltompc_make_step_dev(ltompc_handle h, const double* x0_dev, double* u0_dev) 
     if (it >= h->max_iter) break;  // that pass only finalised the statuses (MAX_ITER)
     if ((it + 1) % h->poll_every == 0) {
       if (L.close()) return -1;
-      HIPCHECK(hipMemcpyAsync(h->h_active, h->W.active + it, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      HIPCHECK(hipMemcpyAsync(h->h_active + 1, h->W.ls_count + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      hipLaunchKernelGGL(k_poll, dim3(1), dim3(64), 0, h->stream, (const int*)(h->W.active + it), (const int*)(h->W.ls_count + 1), h->h_active_dev);
       HIPCHECK(hipStreamSynchronize(h->stream));
       const int n_active = h->h_active[0];  // instances that passed the termination test of iteration `it`
       // Second line-search phase: one thread per (candidate, interval, rejected instance).  Its launch costs in
@@ -1239,8 +1240,7 @@ int ltompc_rollout_dev(ltompc_handle h, double* x_dev, int n_ticks, int n_sub, d
     }
     first = false;
     if ((it + 1) % h->poll_every == 0) {
-      ROLLCHECK(hipMemcpyAsync(h->h_active, d_cnt, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      ROLLCHECK(hipMemcpyAsync(h->h_active + 1, h->W.ls_count + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      hipLaunchKernelGGL(k_poll, dim3(1), dim3(64), 0, h->stream, (const int*)d_cnt, (const int*)(h->W.ls_count + 1), h->h_active_dev);
       ROLLCHECK(hipStreamSynchronize(h->stream));
       const int n_left = h->h_active[0];  // instances that still have ticks to do (counted before this iteration's plant steps)
       h->history.push_back((int)it), h->history.push_back(n_left), h->history.push_back(n_launch);
