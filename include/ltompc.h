@@ -707,6 +707,52 @@ int ltompc_record_release(ltompc_handle h, ltompc_record rec);
 int ltompc_record_trim(ltompc_handle h);
 int ltompc_record_stats(ltompc_handle h, int* in_use, int* free_);
 
+/* The feedback policy of the last solve: the time-varying local law of the whole horizon, to close the loop
+ * between solves.  With X, U the prediction of that solve, V_0 the u_prev it used and V_k = U_{k-1}, for instance b
+ *     pi_k(x, v) = U_k + K_k (x - X_k) + Kv_k (v - V_k),      k = 0 .. N-1.
+ * K_k (2 x 8) and Kv_k (2 x 2) are the stage gains of the delta_w = 0 Riccati factorisation at the final iterate, the words the
+ * forward pass of ltompc_get_sensitivities propagates (dU_k = K_k dX_k + Kv_k dV_k): K_k is the derivative of the first control
+ * of the BARRIER problem of the tail (nodes k .. N) w.r.t. its initial state, Kv_k w.r.t. its previous input.  K_0 = du0/dx0 and
+ * Kv_0 = du0/du_prev bit for bit.  They are not the gains of a solve started at node k with a new barrier parameter or warm start.
+ *   ok[b] equals ltompc_get_sensitivities' ok[b] bit for bit.  Where ok[b] = 0, K and Kv are exactly 0 and pi_k = U_k - not NaN:
+ *   a caller that applies the policy blindly gets the open-loop plan.
+ *   clip = 1 saturates the result; delta and T (states 6, 7) integrate the inputs exactly over one t_step under a held input, so
+ *   for i = 0, 1 first u_i <- min(max(u_i, (x_lb[6+i] - x[6+i]) / t_step), (x_ub[6+i] - x[6+i]) / t_step), then
+ *   u_i <- min(max(u_i, u_lb[i]), u_ub[i]) (the input bounds win); a bound at LTOMPC_NO_BOUND is skipped.  clip = 0: the formula.
+ *
+ * All arrays are row-major in the caller's instance order.
+ * ltompc_get_policy: host outputs, any may be NULL:  K  batch x N x 2 x 8;   Kv  batch x N x 2 x 2;   ok  batch ints.
+ * ltompc_policy_dev: the same into device arrays, any may be NULL.  Enqueues only, on the handle's stream.
+ * ltompc_policy_step: u (batch x 2) = pi_k(x, v) for host arrays x (batch x 8) and v (batch x 2; NULL means V_k: no correction
+ *   in that direction).  A non-finite x or v is a usage error that names the instance.
+ * ltompc_policy_step_dev: device pointers, enqueues only.  x and v are NOT checked.  It reads the prediction and the gains where
+ *   they are: no gather first, and the instances stay where the solve left them.
+ * ltompc_policy_run_dev: n ticks of the loop in ONE launch, for j = 0 .. n-1:
+ *       u_j = pi_{k0+j}(x, v);   x <- plant(x, u_j, t_step, n_sub);   v <- u_j,
+ *   the plant step that of ltompc_plant_step_dev bit for bit (the handle's tables, per-instance rows and table sets in effect -
+ *   also while a record is selected).  x_dev (batch x 8) holds the states, in and out; v_dev (batch x 2) the input before tick 0
+ *   or NULL (V_k0);  u_log_dev (batch x n x 2) the controls and x_log_dev (batch x n x 8) the state AFTER each tick, either may
+ *   be NULL.  Enqueues only.  With n = 1, u_log_dev may be v_dev itself (an instance's row is read before it is written).
+ * ltompc_policy_last_dev: the controls of the last tick of such a log (batch x n x 2) as an array u_dev (batch x 2) - what
+ *   ltompc_set_u_prev_dev and ltompc_plant_step_dev take.  One strided device copy, enqueued on the handle's stream.
+ * Exception: the first request on a handle (any of the five) allocates the pass's workspaces and synchronises the handle's stream
+ *   once (as for ltompc_sensitivities_dev, whose workspaces they are); the first host form also its staging.
+ *
+ * The result refers to the last solve of each instance, or to the selected record, exactly like ltompc_get_sensitivities; the
+ * re-linearisation and the factorisation are shared with the other passes (whichever runs first for a solve makes them).  Usage
+ * errors, which leave the handle unchanged: a call before any solve or after set_initial_guess(_dev); k (k0) outside [0, N);
+ * n < 1; k0 + n > N; n_sub < 1; policy_step / policy_run after rollout_dev (it does not keep the u_prev of each instance's last
+ * solve, V_0) - the gains alone stay available there, like the sensitivities.  Handles with ell_penalty > 0 or ptv != 0 are
+ * accepted.  The calls write buffers of their own and the caller's arrays only: every later make_step, rollout or pass gives the
+ * bits it would have given without them. */
+int ltompc_get_policy(ltompc_handle h, double* K, double* Kv, int* ok);
+int ltompc_policy_dev(ltompc_handle h, double* K_dev, double* Kv_dev, int* ok_dev);
+int ltompc_policy_step(ltompc_handle h, int k, const double* x, const double* v, int clip, double* u);
+int ltompc_policy_step_dev(ltompc_handle h, int k, const double* x_dev, const double* v_dev, int clip, double* u_dev);
+int ltompc_policy_run_dev(ltompc_handle h, int k0, int n, double* x_dev, const double* v_dev, int n_sub, int clip, double* u_log_dev,
+                          double* x_log_dev);
+int ltompc_policy_last_dev(ltompc_handle h, int n, const double* u_log_dev, double* u_dev);
+
 /* Profiling: when on, every kernel launch of make_step is bracketed by HIP events on the handle's stream and
  * ltompc_get_timing returns the accumulated device time per kernel class since profiling was switched on:
  * index 0 eval (k_eval or k_eval8), 1 riccati (8 instances per wavefront), 2 expand (k_expand or k_expand8), 3 linesearch,

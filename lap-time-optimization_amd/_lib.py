@@ -121,6 +121,12 @@ def lib() -> C.CDLL:
         L.ltompc_record_release.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_record_trim.argtypes = [C.c_void_p]
         L.ltompc_record_stats.argtypes = [C.c_void_p, _ip, _ip]
+        L.ltompc_get_policy.argtypes = [C.c_void_p, _dp, _dp, _ip]
+        L.ltompc_policy_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ltompc_policy_step.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp]
+        L.ltompc_policy_step_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.ltompc_policy_run_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.ltompc_policy_last_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

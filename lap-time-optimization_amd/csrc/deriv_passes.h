@@ -346,6 +346,41 @@ int planes_to_rows(ltompc_solver* h, const double* planes, const int f0, const i
   return 0;
 }
 
+// The feedback policy of the last solve (policy.h): ok of the (x0, u_prev) pass and the factorisation, whose
+// Riccati buffer holds the gains, at the instances' current slots (whichever pass runs first for a solve makes them).  `law`: the
+// caller evaluates pi_k, which needs the u_prev that solve used (V_0).  Once the pass's buffers exist it only enqueues.
+int pol_prepare(ltompc_solver* h, const bool law, const char* who) {
+  DerivState& D = h->dv;
+  if (law && D.sens != Sens::no_solve && !D.kept_uprev)
+    return fail(std::string(who) + ": not available after a rollout (it does not keep the u_prev of each instance's last solve, V_0 of the policy; the gains are: ltompc_get_policy)");
+  if (sens_compute(h, false, who)) return -1;  // (the usage error before a solve comes from here)
+  sens_factorise(h);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The stage gains of all instances into K_dev (B x N x 2 x 8) / Kv_dev (B x N x 2 x 2), either may be null
+int pol_gather(ltompc_solver* h, double* K_dev, double* Kv_dev) {
+  if (!K_dev && !Kv_dev) return 0;
+  hipLaunchKernelGGL(k_policy_gather, dim3(h->Bp / 8, (h->N + POL_KS - 1) / POL_KS), dim3(256), 0, h->stream, h->dv.Ws, (const int*)h->dv.d_sens_ok,
+                     K_dev, Kv_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The staging of the policy's host forms, each on its first request with one synchronisation
+int pol_staging(ltompc_solver* h, const bool gains) {
+  DerivState& D = h->dv;
+  const size_t B = h->B, N = h->N;
+  int rc = 0;
+  bool fresh = false;
+  if (gains && !D.d_pol_K) rc |= h->dalloc(&D.d_pol_K, B * N * 16), rc |= h->dalloc(&D.d_pol_Kv, B * N * 4), fresh = true;
+  if (!gains && !D.d_pol_io) rc |= h->dalloc(&D.d_pol_io, B * 12), fresh = true;
+  if (rc) return -1;
+  if (fresh) HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ solve records
 // The arrays of a record inside its one device buffer, each 256-byte aligned, in bytes from the start; `end`: the size.
 struct RecLayout {
@@ -881,6 +916,107 @@ int ltompc_loop_sensitivities_dev(ltompc_handle h, double* dx_dq_dev, double* du
 int ltompc_loop_end(ltompc_handle h) {
   if (!h) return fail("null handle");
   h->dv.loop_mode = 0;
+  return 0;
+}
+
+int ltompc_get_policy(ltompc_handle h, double* K, double* Kv, int* ok) {
+  const char* who = "ltompc_get_policy";
+  if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  HIPCHECK(hipSetDevice(h->device));
+  if (pol_prepare(h, false, who)) return -1;
+  const DerivState& D = h->dv;
+  const size_t B = h->B, N = h->N;
+  if (K || Kv) {
+    if (pol_staging(h, true) || pol_gather(h, K ? D.d_pol_K : nullptr, Kv ? D.d_pol_Kv : nullptr)) return -1;
+  }
+  if (copy_out(h, D2H, K, D.d_pol_K, B * N * 16) || copy_out(h, D2H, Kv, D.d_pol_Kv, B * N * 4) || copy_out(h, D2H, ok, D.d_sens_ok, B)) return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_policy_dev(ltompc_handle h, double* K_dev, double* Kv_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  HIPCHECK(hipSetDevice(h->device));
+  if (pol_prepare(h, false, "ltompc_policy_dev") || pol_gather(h, K_dev, Kv_dev)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_policy_step_dev(ltompc_handle h, int k, const double* x_dev, const double* v_dev, int clip, double* u_dev) {
+  const char* who = "ltompc_policy_step";
+  if (!h || !x_dev || !u_dev) return fail(std::string(who) + ": null argument");
+  if (k < 0 || k >= h->N) return fail(std::string(who) + ": k must be in [0, N)");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  HIPCHECK(hipSetDevice(h->device));
+  if (pol_prepare(h, true, who)) return -1;
+  const DerivState& D = h->dv;
+  hipLaunchKernelGGL(k_policy_step, dim3((h->B + 63) / 64), dim3(64), 0, h->stream, h->K, D.Ws, (const int*)D.d_sens_ok,
+                     (const double*)D.d_psens_uprev, k, x_dev, v_dev, clip ? 1 : 0, u_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+int ltompc_policy_step(ltompc_handle h, int k, const double* x, const double* v, int clip, double* u) {
+  const char* who = "ltompc_policy_step";
+  if (!h || !x || !u) return fail(std::string(who) + ": null argument");
+  if (k < 0 || k >= h->N) return fail(std::string(who) + ": k must be in [0, N)");
+  const size_t B = h->B;
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; e < 8; e++) fin = fin && std::isfinite(x[b * 8 + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite x of instance " + std::to_string(b));
+    for (size_t e = 0; v && e < 2; e++) fin = fin && std::isfinite(v[b * 2 + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite v of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  if (pol_staging(h, false)) return -1;
+  double *dx = h->dv.d_pol_io, *dv = dx + 8 * B, *du = dx + 10 * B;
+  HIPCHECK(hipMemcpyAsync(dx, x, sizeof(double) * 8 * B, hipMemcpyHostToDevice, h->stream));
+  if (v) HIPCHECK(hipMemcpyAsync(dv, v, sizeof(double) * 2 * B, hipMemcpyHostToDevice, h->stream));
+  if (ltompc_policy_step_dev(h, k, dx, v ? dv : nullptr, clip, du)) return -1;
+  HIPCHECK(hipMemcpyAsync(u, du, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int ltompc_policy_run_dev(ltompc_handle h, int k0, int n, double* x_dev, const double* v_dev, int n_sub, int clip, double* u_log_dev,
+                          double* x_log_dev) {
+  const char* who = "ltompc_policy_run";
+  if (!h || !x_dev) return fail(std::string(who) + ": null argument");
+  if (k0 < 0 || k0 >= h->N) return fail(std::string(who) + ": k0 must be in [0, N)");
+  if (n < 1) return fail(std::string(who) + ": n must be >= 1");
+  if (k0 + n > h->N) return fail(std::string(who) + ": k0 + n must be <= N (the policy ends with the horizon)");
+  if (n_sub < 1) return fail(std::string(who) + ": n_sub must be >= 1");
+  // the plant is the handle's: its tables, rows and sets in effect, as ltompc_plant_step_dev, whatever record is selected
+  const Consts K_live = h->K;
+  const int n_sets_live = h->n_sets;
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  HIPCHECK(hipSetDevice(h->device));
+  if (pol_prepare(h, true, who)) return -1;
+  const DerivState& D = h->dv;
+  const dim3 grid((h->B + 63) / 64), block(64);
+  const int* ok = D.d_sens_ok;
+  const double* up = D.d_psens_uprev;
+  const int c = clip ? 1 : 0;
+  if (n_sets_live)
+    hipLaunchKernelGGL(k_policy_run_ts, grid, block, 0, h->stream, K_live, D.Ws, ok, up, k0, n, x_dev, v_dev, n_sub, c, u_log_dev, x_log_dev,
+                       (const double*)(h->pi_pend ? h->d_th_pend : h->d_th_unif), (const double*)h->d_ts_vals, (const int*)h->d_ts_idx);
+  else if (h->pi_pend)
+    hipLaunchKernelGGL(k_policy_run_pi, grid, block, 0, h->stream, K_live, D.Ws, ok, up, k0, n, x_dev, v_dev, n_sub, c, u_log_dev, x_log_dev,
+                       (const double*)h->d_th_pend);
+  else hipLaunchKernelGGL(k_policy_run, grid, block, 0, h->stream, K_live, D.Ws, ok, up, k0, n, x_dev, v_dev, n_sub, c, u_log_dev, x_log_dev);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+int ltompc_policy_last_dev(ltompc_handle h, int n, const double* u_log_dev, double* u_dev) {
+  const char* who = "ltompc_policy_last_dev";
+  if (!h || !u_log_dev || !u_dev) return fail(std::string(who) + ": null argument");
+  if (n < 1) return fail(std::string(who) + ": n must be >= 1");
+  HIPCHECK(hipSetDevice(h->device));
+  const size_t row = 2 * sizeof(double);  // rows of 16 bytes, n rows apart in the log
+  HIPCHECK(hipMemcpy2DAsync(u_dev, row, u_log_dev + (size_t)2 * (n - 1), row * n, row, h->B, hipMemcpyDeviceToDevice, h->stream));
   return 0;
 }
 

@@ -42,6 +42,10 @@
 //   warm_state_host.h (host, part of ltompc.hip only) their C entry points
 //   record.h      k_rec_save: everything the derivative passes read of a solve, gathered into a record in the caller's order
 //                 (ltompc_record_save); the passes then run on a Work that points into the record
+//   policy.h      k_policy_gather, k_policy_step, k_policy_run: the feedback policy of a solve (ltompc_get_policy, ltompc_policy_step,
+//                 ltompc_policy_run_dev): the stage gains K_k, Kv_k of the sensitivity pass's factorisation in the
+//                 caller's order (an LDS tile transpose), u = U_k + K_k (x - X_k) + Kv_k (v - V_k) on the iterate and the gains where
+//                 they are, and n ticks of that law and d_plant in one launch
 //   *_pi          the kernels above that read a vehicle or cost parameter, once more with per-instance values of the 16 of
 //                 param_sensitivity.h (ltompc_set_instance_params): the same device functions instantiated with
 //                 PI = true, reading the rows through WorkPI (layout.h); the uniform kernels are unchanged
@@ -68,3 +72,4 @@
 #include "table_sensitivity.h"
 #include "warm_state.h"
 #include "record.h"
+#include "policy.h"

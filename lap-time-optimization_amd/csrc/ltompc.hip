@@ -75,6 +75,8 @@ struct DerivState {
   WorkTS Wsts{}, *d_Wsts = nullptr;
   double* d_tab_gs = nullptr;
   int tab_gs_cap = 0;
+  // feedback policy (policy.h): the staging of the host forms, gains (B x N x 16, B x N x 4) and x | v | u (B x 12)
+  double *d_pol_K = nullptr, *d_pol_Kv = nullptr, *d_pol_io = nullptr;
 };
 
 struct ltompc_record_s;  // a solve record (deriv_passes.h)

@@ -447,6 +447,67 @@ class BatchedMPC:
         order, on the handle's stream (prediction() without the host; the instances stay packed as they are)."""
         check(lib().ltompc_get_prediction_dev(self._h, C.c_void_p(X_ptr or None), C.c_void_p(U_ptr or None)))
 
+    # ---- the feedback policy of the last solve (ltompc_get_policy, ltompc_policy_*, DESIGN.md §18) --------------------------
+    def policy(self):
+        """The time-varying feedback law of the last solve (or of the selected record), for every stage of the horizon:
+        pi_k(x, v) = U_k + K_k (x - X_k) + Kv_k (v - V_k) with X, U = prediction(), V_0 the u_prev of that solve, V_k = U_{k-1}.
+
+        Returns K (B,N,2,8), Kv (B,N,2,2) - the stage gains of the delta_w = 0 factorisation at the final iterate, K[:, 0] =
+        du0_dx0 and Kv[:, 0] = du0_duprev of sensitivities() bit for bit - and ok (B,) bool (the same as sensitivities()' ok).
+        Where ok is False the gains are 0: the policy is the open-loop plan."""
+        B, N = self.B, self.N
+        K, Kv, ok = np.empty((B, N, NU, NX)), np.empty((B, N, NU, NU)), np.empty(B, dtype=np.int32)
+        check(lib().ltompc_get_policy(self._h, dptr(K), dptr(Kv), iptr(ok)))
+        return dict(K=K, Kv=Kv, ok=ok != 0)
+
+    def policy_dev(self, K_ptr: int = 0, Kv_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue policy() into device arrays (B,N,2,8) / (B,N,2,2) doubles / (B,) int32 (0: not wanted), on the handle's stream."""
+        check(lib().ltompc_policy_dev(self._h, C.c_void_p(K_ptr or None), C.c_void_p(Kv_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    def policy_step(self, k: int, x, v=None, clip: bool = False):
+        """u (B,2) = pi_k(x (B,8), v (B,2)) of the last solve; v=None: V_k (no correction in that direction).  clip=True
+        saturates u at the bounds of delta and T one t_step ahead, then at the input bounds (include/ltompc.h).  A non-finite x
+        or v is refused."""
+        x = self._x(x)
+        vv = None if v is None else _shaped("policy_step", "v", v, (self.B, NU))
+        u = np.empty((self.B, NU))
+        check(lib().ltompc_policy_step(self._h, int(k), dptr(x), dptr(vv) if vv is not None else None, int(bool(clip)), dptr(u)))
+        return u
+
+    def policy_step_dev(self, k: int, x_ptr: int, v_ptr: int, u_ptr: int, clip: bool = False):
+        """Enqueue policy_step on the handle's stream: device arrays x (B,8), v (B,2; 0: V_k) in, u (B,2) out.  NOT checked.  It
+        reads prediction and gains where they are: no gather, the instances stay packed as they are."""
+        check(lib().ltompc_policy_step_dev(self._h, int(k), C.c_void_p(x_ptr), C.c_void_p(v_ptr or None), int(bool(clip)), C.c_void_p(u_ptr)))
+
+    def policy_run_dev(self, k0: int, n: int, x_ptr: int, v_ptr: int = 0, n_sub: int = 400, clip: bool = False, u_log_ptr: int = 0,
+                       x_log_ptr: int = 0):
+        """n solve-free ticks in ONE launch on the handle's stream: for j < n, u_j = pi_{k0+j}(x, v); x <- plant step (the bits
+        of plant_step_dev); v <- u_j.  x (B,8) device array, in and out; v (B,2) the input before the first tick (0: V_k0);
+        u_log (B,n,2) and x_log (B,n,8; the state after each tick) or 0.  k0 + n <= N."""
+        check(lib().ltompc_policy_run_dev(self._h, int(k0), int(n), C.c_void_p(x_ptr), C.c_void_p(v_ptr or None), int(n_sub), int(bool(clip)),
+                                          C.c_void_p(u_log_ptr or None), C.c_void_p(x_log_ptr or None)))
+
+    def policy_last_dev(self, n: int, u_log_ptr: int, u_ptr: int):
+        """Enqueue, on the handle's stream, the copy of the last tick's controls of a policy_run_dev log (B,n,2) into a device
+        array (B,2): what set_u_prev_dev and plant_step_dev take."""
+        check(lib().ltompc_policy_last_dev(self._h, int(n), C.c_void_p(u_log_ptr), C.c_void_p(u_ptr)))
+
+    def policy_run(self, k0: int, n: int, x, v=None, n_sub: int = 400, clip: bool = False):
+        """Host convenience for policy_run_dev: the same loop written with policy_step and plant_step (the same kernels' device
+        functions, so the same bits), from x (B,8) and v (B,2) or None (V_k0).  Returns dict(u=(B,n,2), x=(B,n,8) the state
+        after each tick)."""
+        k0, n = int(k0), int(n)
+        if k0 < 0 or n < 1 or k0 + n > self.N:
+            raise ValueError(f"policy_run: need 0 <= k0, 1 <= n and k0 + n <= {self.N}, got k0 = {k0}, n = {n}")
+        x = self._x(x)
+        v = None if v is None else _shaped("policy_run", "v", v, (self.B, NU))
+        ul, xl = np.empty((self.B, n, NU)), np.empty((self.B, n, NX))
+        for j in range(n):
+            v = self.policy_step(k0 + j, x, v, clip)
+            x = self.plant_step(x, v, n_sub)
+            ul[:, j], xl[:, j] = v, x
+        return dict(u=ul, x=xl)
+
     # ---- plant-step and closed-loop sensitivities (ltompc_plant_sensitivities, ltompc_loop_*, DESIGN.md §12) ---------------
     def plant_sensitivities(self, x, u, n_sub: int = 400, theta: bool = True):
         """The plant step and the derivative of its discrete RK4 map at (x (B,8), u (B,2)): x_next (B,8, the bits of
@@ -1003,15 +1064,59 @@ class SplitMPC:
         self._each(lambda p, lo, hi: p.make_step_dev(x0_ptr + 8 * NX * lo, u0_ptr + 8 * NU * lo))
 
     def run_ticks(self, x_ptr: int, u_ptr, xn_ptr: int, n_ticks: int, n_sub: int = 400, after_tick=None, before_tick=None,
-                  loop: bool = False):
+                  loop: bool = False, solve_every: int = 1, u_log_ptr: int = 0):
         """n_ticks of the closed loop [make_step; plant step] for every part at its own pace: x (B, 8) and xn (B, 8) are swapped
         after every tick (the states end in x if n_ticks is even, else in xn), u (B, 2) holds the last controls.  u_ptr may be a
         sequence of pointers: tick t then writes its controls to u_ptr[t % len(u_ptr)] (a ring: somebody else - a gather over the
         ranks, a logger - reads the controls of tick t while the parts are one tick further).
         before_tick(part_index, tick) / after_tick(part_index, tick) run in the part's thread around each of its ticks (before_tick
         may block: that is how a consumer of the ring holds a part back).  loop=True: loop_tick_dev in place of plant_step_dev
-        (after loop_begin): the same states, and the closed-loop sensitivities accumulate.  Returns when all parts are done."""
+        (after loop_begin): the same states, and the closed-loop sensitivities accumulate.  Returns when all parts are done.
+
+        solve_every=m > 1: the ticks come in groups of m.  The first tick of a group is make_step_dev +
+        plant_step_dev as above; the m - 1 ticks after it (fewer in a last, shorter group) are ONE policy_run_dev(k0=1, n=m-1,
+        clip=True) of that solve's feedback policy, started from its u0, which advances the states where the solve tick left
+        them.  x and xn are therefore swapped once per GROUP (the states end in x if the number of groups is even), u_ptr (the
+        ring: by group) receives the last control of each group, and set_u_prev_dev(that control) runs before the next solve.
+        before_tick / after_tick run around each group, with the index of its first tick.  u_log_ptr: a device array (B, m-1, 2)
+        that receives the policy controls of each part's current group, required for m > 2 (the last control of a group is
+        gathered from it).  m must not exceed the horizon.  The warm start of the next solve is left as it is: the last
+        solution shifted by ONE interval, so m intervals old for a solve m ticks later - it costs iterations; a caller who
+        wants a better one sets it with set_guess_dev.  loop=True with solve_every != 1 is a ValueError (the policy ticks have
+        no closed-loop sensitivities)."""
         ring = [int(u_ptr)] if isinstance(u_ptr, int) else [int(q) for q in u_ptr]
+        m = int(solve_every)
+        if m != 1:
+            if loop:
+                raise ValueError("run_ticks: loop=True needs solve_every=1 (the policy ticks have no closed-loop sensitivities)")
+            if m < 1 or m > self.N:
+                raise ValueError(f"run_ticks: solve_every must be in [1, {self.N}] (the policy ends with the horizon), got {solve_every}")
+            if m > 2 and not u_log_ptr:
+                raise ValueError("run_ticks: solve_every > 2 needs u_log_ptr, a device array (B, solve_every - 1, 2)")
+            def group_body(p, lo, hi):
+                a, b = x_ptr + 8 * NX * lo, xn_ptr + 8 * NX * lo
+                pi = self.parts.index(p)
+                for g, t in enumerate(range(0, n_ticks, m)):
+                    if before_tick is not None:
+                        before_tick(pi, t)
+                    u = ring[g % len(ring)] + 8 * NU * lo
+                    p.make_step_dev(a, u)
+                    p.plant_step_dev(a, u, b, n_sub)
+                    a, b = b, a
+                    n = min(m, n_ticks - t) - 1
+                    if n == 1:  # (a (B,1,2) log is the (B,2) array itself: v is read before u is written, by the same thread)
+                        p.policy_run_dev(1, 1, a, u, n_sub, True, u_log_ptr=u)
+                    elif n > 1:
+                        log = u_log_ptr + 8 * NU * (m - 1) * lo
+                        p.policy_run_dev(1, n, a, u, n_sub, True, u_log_ptr=log)
+                        p.policy_last_dev(n, log, u)
+                    if n >= 1:
+                        p.set_u_prev_dev(u)
+                    if after_tick is not None:
+                        after_tick(pi, t)
+                p.synchronize()
+            self._each(group_body)
+            return
         def body(p, lo, hi):
             a, b = x_ptr + 8 * NX * lo, xn_ptr + 8 * NX * lo
             pi = self.parts.index(p)
@@ -1393,3 +1498,50 @@ class SplitMPC:
         N = self.N
         for p, (lo, hi) in zip(self.parts, self.bounds):
             p.prediction_dev(X_ptr + 8 * (N + 1) * NX * lo if X_ptr else 0, U_ptr + 8 * N * NU * lo if U_ptr else 0)
+
+    # ---- the feedback policy (BatchedMPC.policy): by global index, each part fills its rows
+    def policy(self):
+        """BatchedMPC.policy of every part, stitched in the caller's order."""
+        r = [p.policy() for p in self.parts]
+        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    def policy_dev(self, K_ptr: int = 0, Kv_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.policy_dev of every part into its rows of (B,N,2,8) / (B,N,2,2) doubles / (B,) int32, each on its part's stream."""
+        N = self.N
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.policy_dev(K_ptr + 8 * N * NU * NX * lo if K_ptr else 0, Kv_ptr + 8 * N * NU * NU * lo if Kv_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def policy_step(self, k: int, x, v=None, clip: bool = False):
+        """BatchedMPC.policy_step with the rows split across the parts (shapes and finiteness checked first: a bad row reaches no part)."""
+        x = _shaped("policy_step", "x", x, (self.B, NX))
+        v = None if v is None else _shaped("policy_step", "v", v, (self.B, NU))
+        if not (np.isfinite(x).all() and (v is None or np.isfinite(v).all())):
+            raise ValueError("policy_step: non-finite x or v")
+        return np.concatenate([p.policy_step(k, x[lo:hi], None if v is None else v[lo:hi], clip) for p, (lo, hi) in zip(self.parts, self.bounds)])
+
+    def policy_step_dev(self, k: int, x_ptr: int, v_ptr: int, u_ptr: int, clip: bool = False):
+        """BatchedMPC.policy_step_dev of every part on its rows of x (B,8), v (B,2; 0: V_k), u (B,2), each on its part's stream."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.policy_step_dev(k, x_ptr + 8 * NX * lo, v_ptr + 8 * NU * lo if v_ptr else 0, u_ptr + 8 * NU * lo, clip)
+
+    def policy_run_dev(self, k0: int, n: int, x_ptr: int, v_ptr: int = 0, n_sub: int = 400, clip: bool = False, u_log_ptr: int = 0,
+                       x_log_ptr: int = 0):
+        """BatchedMPC.policy_run_dev of every part on its rows of x (B,8), v (B,2), u_log (B,n,2), x_log (B,n,8), each on its
+        part's stream."""
+        n = int(n)
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.policy_run_dev(k0, n, x_ptr + 8 * NX * lo, v_ptr + 8 * NU * lo if v_ptr else 0, n_sub, clip,
+                             u_log_ptr + 8 * NU * n * lo if u_log_ptr else 0, x_log_ptr + 8 * NX * n * lo if x_log_ptr else 0)
+
+    def policy_last_dev(self, n: int, u_log_ptr: int, u_ptr: int):
+        """BatchedMPC.policy_last_dev of every part on its rows of u_log (B,n,2) and u (B,2), each on its part's stream."""
+        n = int(n)
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            p.policy_last_dev(n, u_log_ptr + 8 * NU * n * lo, u_ptr + 8 * NU * lo)
+
+    def policy_run(self, k0: int, n: int, x, v=None, n_sub: int = 400, clip: bool = False):
+        """BatchedMPC.policy_run with the rows split across the parts, stitched in the caller's order."""
+        x = _shaped("policy_run", "x", x, (self.B, NX))
+        v = None if v is None else _shaped("policy_run", "v", v, (self.B, NU))
+        r = [p.policy_run(k0, n, x[lo:hi], None if v is None else v[lo:hi], n_sub, clip) for p, (lo, hi) in zip(self.parts, self.bounds)]
+        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
