@@ -478,6 +478,55 @@ int ltompc_get_prediction_dev(ltompc_handle h, double* X_dev, double* U_dev);
 int ltompc_get_jvp(ltompc_handle h, const double* dp, const double* dtheta, double* tX, double* tU, int* ok);
 int ltompc_jvp_dev(ltompc_handle h, const double* dp_dev, const double* dtheta_dev, double* tX_dev, double* tU_dev, int* ok_dev);
 
+/* Directional sensitivities along a direction in the track tables: the forward twin of ltompc_get_adjoint_tables.
+ * For a direction dy[r][j] in the knot values of the 4 value rows r = kappa, n_left, n_right, v_ref (the rows of
+ * ltompc_set_table_values; the grids are not differentiated), for instance b:
+ *     tX[k,i] = sum_{r,j} dX_b[k,i]/dy[r][j] dy[r][j] (+ sum_{j < 10} dX_dp[k,i,j] dp[j]),     tU[k,c] likewise
+ * with dX/dy, dU/dy exactly the sensitivities whose transpose ltompc_get_adjoint_tables applies: the barrier problem at the final
+ * iterate with the final barrier parameter and table smoothing, the KKT matrix with delta_w = 0, the same instances.  ok[b] equals
+ * ltompc_get_sensitivities' ok[b] bit for bit; every output of an instance with ok[b] = 0 is exactly 0.  Block 0 of tX is dp[0..7]
+ * when dp is given, else 0.  dtheta is not part of this call: the map is linear, a caller adds ltompc_jvp_dev's result.
+ *
+ * The direction has two forms, summed when both are given:
+ *   dtables  4 x n_table: ONE direction of the handle, shared by all instances as the tables are.  The look-ups are linear in the
+ *            knot values, so it reaches interval k as the ten tangents below with the weights of the piece-wise linear basis
+ *            (with the rounding of the knots that the solve used: at most four knots per look-up).  With periodic_tables the
+ *            first and the last knot of a row are read separately, as grad_tables reports them separately.
+ *   dslot    batch x N x 10, in slot_grad's order: the tangents of what each look-up returned,
+ *                d( kappa(s(c_k)), kappa'(s(c_k)), kappa(s(x_{k+1})), kappa'(s(x_{k+1})),
+ *                   n_left, n_left', n_right, n_right', v_ref, v_ref' at s(x_{k+1}) )
+ *            (the last six do not enter for k = N - 1).  The forward twin of slot_grad, for a caller that owns its table
+ *            parametrisation (a spline race line) and pushes tangents through it itself.
+ * The pass is a gather without atomic adds: the same solve and direction give the same bits, whatever the batch, the packing or
+ * the split over handles.
+ *
+ * Inputs:  dp  batch x 10 (x0[0..7], u_prev[0..1]), dslot in the caller's instance order; dtables as above.  Any may be NULL
+ * (= zeros); all three NULL is a usage error.  With dp alone the call is ltompc_get_jvp's without dtheta.
+ * Outputs, in the caller's instance order, any may be NULL:  tX  batch x (N+1) x 8;   tU  batch x N x 2;   ok  batch ints.
+ * ltompc_get_jvp_tables: host pointers.  A non-finite direction is a usage error that names the row and knot (dtables) or the
+ *   instance (dp, dslot).
+ * ltompc_jvp_tables_dev: device pointers, enqueues only, on the handle's stream.  The directions are NOT checked.  The first
+ *   request on a handle allocates the pass's buffers and synchronises once (as for ltompc_sensitivities_dev).
+ *
+ * The result refers to the last solve of each instance (under a selected solve record: to the record's); before any solve, after
+ * set_initial_guess(_dev) and between ltompc_set_table_values(_dev) / ltompc_set_table_sets and the next solve a call is a usage
+ * error.  A handle with ell_penalty > 0 or ptv != 0 is a usage error, as for ltompc_get_adjoint_tables; the pass needs no u_prev,
+ * so a call after rollout_dev works.  With per-instance rows the result is that at the rows the solve used.  The
+ * re-linearisation and the factorisation are shared with the other passes (whichever runs first for a solve makes them);
+ * nothing is kept per direction.  The pass writes buffers of its own only: every later make_step, rollout or other pass gives
+ * the bits it would have given without it.
+ *
+ * On a handle with per-instance table sets (ltompc_set_table_sets) the two calls above are usage errors that name the two below,
+ * and the other way round: there dtables is n_sets x 4 x n_table and instance b moves along block set_of_instance[b], on the
+ * rows of its own set; a non-finite entry names the set too. */
+int ltompc_get_jvp_tables(ltompc_handle h, const double* dp, const double* dtables, const double* dslot, double* tX, double* tU, int* ok);
+int ltompc_jvp_tables_dev(ltompc_handle h, const double* dp_dev, const double* dtables_dev, const double* dslot_dev, double* tX_dev,
+                          double* tU_dev, int* ok_dev);
+int ltompc_get_jvp_table_sets(ltompc_handle h, const double* dp, const double* dtables, const double* dslot, double* tX, double* tU,
+                              int* ok);
+int ltompc_jvp_table_sets_dev(ltompc_handle h, const double* dp_dev, const double* dtables_dev, const double* dslot_dev, double* tX_dev,
+                              double* tU_dev, int* ok_dev);
+
 /* The previous input u_prev of the NEXT solve's Delta-u cost r_du (u_0 - u_prev)^2, which the handle otherwise makes itself (0
  * after set_initial_guess, else the u0 the last make_step returned): with it the solve is a function of (x0, u_prev, theta) that
  * a caller can evaluate.

@@ -83,6 +83,10 @@ def lib() -> C.CDLL:
         L.ltompc_get_prediction_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ltompc_get_jvp.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _ip]
         L.ltompc_jvp_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("ltompc_get_jvp_tables", "ltompc_get_jvp_table_sets"):
+            getattr(L, name).argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip]
+        for name in ("ltompc_jvp_tables_dev", "ltompc_jvp_table_sets_dev"):
+            getattr(L, name).argtypes = [C.c_void_p] * 7
         L.ltompc_set_u_prev.argtypes = [C.c_void_p, _dp]
         L.ltompc_set_u_prev_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.ltompc_set_table_values.argtypes = [C.c_void_p, C.c_int, _dp]

@@ -1,7 +1,8 @@
 """torch.autograd layer over a BatchedMPC handle: the solve and the plant step as differentiable functions of device tensors.
 
     u0, X, U, ok = mpc_solve(mpc, x0, u_prev, theta, tables)   # make_step_dev + prediction_dev; backward: adjoint_dev (and
-                                                               # adjoint_tables_dev for tables), forward mode: jvp_dev
+                                                               # adjoint_tables_dev for tables), forward mode: jvp_dev,
+                                                               # jvp_tables_dev for a tangent in tables (forward_tables=True)
     x_next       = plant_step(mpc, x, u0, theta, n_sub)   # plant_sensitivities_dev; backward: its Jacobians through torch.einsum
 
 so that one tick `u0 = solve(x, u_prev, th); x = plant(x, u0, th)` is differentiable end to end and a T-tick loop backpropagates
@@ -62,7 +63,7 @@ def _on(mpc, rec):
 
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mpc, x0, u_prev, theta, tables, keep=False):
+    def forward(ctx, mpc, x0, u_prev, theta, tables, keep=False, forward_tables=False):
         B, N = mpc.B, mpc.N
         _check(mpc, "mpc_solve: x0", x0, (B, NX))
         if tables is not None:
@@ -89,6 +90,7 @@ class _Solve(torch.autograd.Function):
         ctx.rec = mpc.record() if keep else None  # (keep: this solve's own record; released when the graph that holds ctx is freed)
         mpc.synchronize()
         ctx.mpc, ctx.count, ctx.has = mpc, mpc.solve_count, (u_prev is not None, theta is not None, tables is not None)
+        ctx.forward_tables = bool(forward_tables)
         ctx.mark_non_differentiable(ok)
         return u0, X, U, ok
 
@@ -114,14 +116,14 @@ class _Solve(torch.autograd.Function):
             if want_tables:
                 mpc.adjoint_tables_dev(gX.data_ptr(), gU.data_ptr(), gtab.data_ptr(), 0, 0)
             mpc.synchronize()
-        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth, gtab, None
+        return None, gp[:, :NX], gp[:, NX:] if ctx.has[0] else None, gth, gtab, None, None
 
     @staticmethod
-    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta, t_tables, _keep=None):
+    def jvp(ctx, _mpc, t_x0, t_uprev, t_theta, t_tables, _keep=None, _forward_tables=None):
         mpc = ctx.mpc
-        if t_tables is not None and ctx.has[2] and bool((t_tables != 0).any()):  # (torch hands zeros for an input without a tangent)
-            raise RuntimeError("mpc_solve jvp: forward mode is not available for `tables` (there is no directional pass in the "
-                               "tables; use reverse mode, which returns grad_tables)")
+        if not ctx.forward_tables and t_tables is not None and ctx.has[2] and bool((t_tables != 0).any()):  # (torch hands zeros for an input without a tangent)
+            raise RuntimeError("mpc_solve jvp: forward mode is not available for `tables` unless the solve was made with "
+                               "forward_tables=True (the directional pass in the tables, jvp_tables_dev); reverse mode returns grad_tables")
         if ctx.rec is None:
             _fresh(mpc, ctx.count, "jvp")
         B, N = mpc.B, mpc.N
@@ -129,17 +131,28 @@ class _Solve(torch.autograd.Function):
             t_uprev = None
         if not ctx.has[1]:
             t_theta = None
+        if not ctx.has[2] or (t_tables is not None and not bool((t_tables != 0).any())):  # (torch hands zeros for an input without a tangent)
+            t_tables = None
         dp = None
         if t_x0 is not None or t_uprev is not None:
             dp = torch.cat([_dense(mpc, t_x0, (B, NX)), _dense(mpc, t_uprev, (B, NU))], dim=1).contiguous()
         dth = None if t_theta is None else _dense(mpc, t_theta, (B, NTHETA))
+        dtab = None if t_tables is None else _dense(mpc, t_tables, (NROWS, mpc.n_table))
         tX, tU = _new(mpc, B, N + 1, NX), _new(mpc, B, N, NU)
-        if dp is None and dth is None:
+        if dp is None and dth is None and dtab is None:
             return _dense(mpc, None, (B, NU)), tX.zero_(), tU.zero_(), None
         _sync_torch(mpc)
         with _on(mpc, ctx.rec):
-            mpc.jvp_dev(dp.data_ptr() if dp is not None else 0, dth.data_ptr() if dth is not None else 0, tX.data_ptr(), tU.data_ptr(), 0)
+            if dtab is None:
+                mpc.jvp_dev(dp.data_ptr() if dp is not None else 0, dth.data_ptr() if dth is not None else 0, tX.data_ptr(), tU.data_ptr(), 0)
+            else:  # (J_p dp + J_y dy in one sweep; the map is linear, so theta's part is jvp_dev's, added)
+                mpc.jvp_tables_dev(dp.data_ptr() if dp is not None else 0, dtab.data_ptr(), 0, tX.data_ptr(), tU.data_ptr(), 0)
+                if dth is not None:
+                    tXt, tUt = _new(mpc, B, N + 1, NX), _new(mpc, B, N, NU)
+                    mpc.jvp_dev(0, dth.data_ptr(), tXt.data_ptr(), tUt.data_ptr(), 0)
             mpc.synchronize()
+        if dtab is not None and dth is not None:
+            tX, tU = tX + tXt, tU + tUt
         return tU[:, 0].clone(), tX, tU, None
 
 
@@ -192,7 +205,7 @@ class _Plant(torch.autograd.Function):
         return out
 
 
-def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None, keep=False):
+def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None, keep=False, forward_tables=False):
     """One solve of the handle as a differentiable function: (u0 (B,2), X (B,N+1,8), U (B,N,2), ok (B,) int32) of x0 (B,8),
     u_prev (B,2; None: the one the handle makes itself, no gradient), theta (B,16 per-instance rows in THETA_NAMES order;
     None: the rows or params in effect, no gradient) and tables ((4, n_table): the value rows kappa, n_left, n_right, v_ref
@@ -202,7 +215,8 @@ def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None, keep=False):
     prediction_dev (and ok of the sensitivity pass).  Backward: adjoint_dev with the cotangent of u0 added to gU[:, 0];
     grad_theta is requested only when theta needs a gradient, and adjoint_tables_dev only when tables does (its result is the
     sum over the instances, which share the tables).  Forward mode (torch.autograd.forward_ad): jvp_dev; a tangent in `tables`
-    raises a RuntimeError (there is no directional pass in the tables).  ok is not differentiable; where it is 0 all
+    raises a RuntimeError unless forward_tables=True, and then goes to jvp_tables_dev (the tangents of x0, u_prev and the tables in
+    one sweep) plus jvp_dev's theta part (the switch keeps a caller that relied on the error as it was).  ok is not differentiable; where it is 0 all
     derivatives are 0.  Torch's current stream is synchronised before the calls and the handle after them.
 
     keep=True: the forward saves a solve record (BatchedMPC.record) and keeps it with the graph.  backward and
@@ -213,6 +227,8 @@ def mpc_solve(mpc, x0, u_prev=None, theta=None, tables=None, keep=False):
 
     The tables set here stay on the handle: they are the CONTROLLER's belief of the track from then on, and the handle's plant
     step reads the kappa row too (plant_step below takes no tables and has no gradient w.r.t. them)."""
+    if forward_tables:
+        return _Solve.apply(mpc, x0, u_prev, theta, tables, bool(keep), True)
     if not keep:
         return _Solve.apply(mpc, x0, u_prev, theta, tables)
     return _Solve.apply(mpc, x0, u_prev, theta, tables, True)

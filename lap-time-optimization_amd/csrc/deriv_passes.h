@@ -305,6 +305,97 @@ int jvp_compute(ltompc_solver* h, const double* dp_dev, const double* dth_dev, d
   return 0;
 }
 
+// The directional pass in the track tables of the last solve (table_jvp.h) for one direction (device pointers, caller's order):
+// dp (B x 10), dtables (4 x n_table; `sets`: n_sets x 4 x n_table) and dslot (B x N x 10), any of them null but not all, into
+// tX_dev / tU_dev (either may be null): the factorisation when not there, the slots' stage vectors, then one sweep.  With dp alone
+// it is jvp.h's dp-only sweep.  It needs no u_prev, so it also runs after a rollout.  Once its planes exist it only enqueues.
+// `sets`: the caller is one of the per-set entry points; each kind of handle has its own.
+int tjv_compute(ltompc_solver* h, const double* dp_dev, const double* dt_dev, const double* ds_dev, double* tX_dev, double* tU_dev,
+                const char* who, const bool sets = false) {
+  DerivState& D = h->dv;
+  if (!sets && h->n_sets)
+    return fail(std::string(who) + ": this handle has per-instance table sets, its table direction is one per set: ltompc_get_jvp_table_sets / ltompc_jvp_table_sets_dev");
+  if (sets && !h->n_sets)
+    return fail(std::string(who) + ": this handle has no table sets (ltompc_set_table_sets), its directional pass in the tables is ltompc_get_jvp_tables / ltompc_jvp_tables_dev");
+  if (!dp_dev && !dt_dev && !ds_dev) return fail(std::string(who) + ": dp, dtables and dslot are all NULL (no direction)");
+  if (h->K.p.ell_penalty > 0.0) return fail(std::string(who) + ": not available with the friction-ellipse constraints (ell_penalty > 0)");
+  if (h->K.p.ptv != 0.0) return fail(std::string(who) + ": not available with torque vectoring (ptv != 0)");
+  if (!dt_dev && !ds_dev) return jvp_compute(h, dp_dev, nullptr, tX_dev, tU_dev, who);  // (the existing dp-only instantiation)
+  if (sens_compute(h, false, who)) return -1;  // (ok; the usage error before a solve comes from here)
+  const int N = h->N, Bp = h->Bp;
+  if (!D.d_tjv_tq) {
+    if (h->dalloc(&D.d_tjv_tq, (size_t)TQ_NF * N * Bp, true) || h->dalloc(&D.d_tjv_jv, (size_t)JV_NF * N * Bp, true)) return -1;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  }
+  sens_factorise(h);
+  const dim3 slots((N * Bp + 63) / 64), block(64);
+  const int* ok = D.d_sens_ok;
+  if (sets) {  // (the stage vectors on each instance's rows and block of the direction; the sweep reads no table: the _pi one)
+    hipLaunchKernelGGL(h->ref_eval ? k_tabjvp_cond_ts<BoundsRef> : k_tabjvp_cond_ts<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
+                       (const WorkTS*)h->d_Wts, ok, dt_dev, ds_dev, D.d_tjv_tq);
+    hipLaunchKernelGGL(k_jvp_sweep_tab_pi, dim3(Bp / 8), block, 0, h->stream, D.Wspi, (const double*)D.d_tjv_tq, ok, dp_dev, D.d_tjv_jv, tX_dev,
+                       tU_dev);
+  } else if (h->pi_solve) {
+    hipLaunchKernelGGL(h->ref_eval ? k_tabjvp_cond_pi<BoundsRef> : k_tabjvp_cond_pi<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
+                       (const WorkPI*)h->d_Wpi, ok, dt_dev, ds_dev, D.d_tjv_tq);
+    hipLaunchKernelGGL(k_jvp_sweep_tab_pi, dim3(Bp / 8), block, 0, h->stream, D.Wspi, (const double*)D.d_tjv_tq, ok, dp_dev, D.d_tjv_jv, tX_dev,
+                       tU_dev);
+  } else {
+    hipLaunchKernelGGL(h->ref_eval ? k_tabjvp_cond<BoundsRef> : k_tabjvp_cond<BoundsAny>, slots, block, 0, h->stream, (const Consts*)h->d_K,
+                       (const Work*)h->d_W, ok, dt_dev, ds_dev, D.d_tjv_tq);
+    hipLaunchKernelGGL(k_jvp_sweep_tab, dim3(Bp / 8), block, 0, h->stream, D.Ws, h->K.p.r_du[0], h->K.p.r_du[1], (const double*)D.d_tjv_tq, ok,
+                       dp_dev, D.d_tjv_jv, tX_dev, tU_dev);
+  }
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// The host form of the above: every direction checked finite, staged, the pass, the results copied back.
+int tjv_host(ltompc_solver* h, const double* dp, const double* dtables, const double* dslot, double* tX, double* tU, int* ok, const char* who,
+             const bool sets) {
+  if (!dp && !dtables && !dslot) return fail(std::string(who) + ": dp, dtables and dslot are all NULL (no direction)");
+  if (!sets && h->n_sets)
+    return fail(std::string(who) + ": this handle has per-instance table sets, its table direction is one per set: ltompc_get_jvp_table_sets / ltompc_jvp_table_sets_dev");
+  if (sets && !h->n_sets)
+    return fail(std::string(who) + ": this handle has no table sets (ltompc_set_table_sets), its directional pass in the tables is ltompc_get_jvp_tables / ltompc_jvp_tables_dev");
+  const size_t B = h->B, N = h->N, n = h->n_table, ns = sets ? h->n_sets : 1;
+  static const char* const rows[TAB_ROWS] = {"kappa", "n_left", "n_right", "v_ref"};
+  for (size_t e = 0; dtables && e < ns * TAB_ROWS * n; e++)
+    if (!std::isfinite(dtables[e])) {
+      const size_t r = e / n % TAB_ROWS;
+      return fail(std::string(who) + ": non-finite dtables" + (sets ? " of set " + std::to_string(e / (TAB_ROWS * n)) + "," : "") + " row " +
+                  std::to_string(r) + " (" + rows[r] + "), knot " + std::to_string(e % n));
+    }
+  for (size_t b = 0; b < B; b++) {
+    bool fin = true;
+    for (size_t e = 0; dp && e < JVP_NP; e++) fin = fin && std::isfinite(dp[b * JVP_NP + e]);
+    for (size_t e = 0; dslot && e < N * TS_NS; e++) fin = fin && std::isfinite(dslot[b * N * TS_NS + e]);
+    if (!fin) return fail(std::string(who) + ": non-finite direction of instance " + std::to_string(b));
+  }
+  HIPCHECK(hipSetDevice(h->device));
+  DerivState& D = h->dv;
+  if (!D.d_tjv_dp && (h->dalloc(&D.d_tjv_dp, JVP_NP * B) || h->dalloc(&D.d_tjv_ds, TS_NS * N * B) || h->dalloc(&D.d_tjv_tX, (N + 1) * 8 * B) ||
+                      h->dalloc(&D.d_tjv_tU, N * 2 * B)))
+    return -1;
+  if (dtables && (int)ns > D.tjv_dt_cap) {  // (grows with the number of sets, as the value buffer)
+    double* fresh = nullptr;
+    if (h->dalloc(&fresh, TAB_ROWS * n * ns)) return -1;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->dfree(D.d_tjv_dt);
+    D.d_tjv_dt = fresh, D.tjv_dt_cap = (int)ns;
+  }
+  if (dp) HIPCHECK(hipMemcpyAsync(D.d_tjv_dp, dp, sizeof(double) * JVP_NP * B, hipMemcpyHostToDevice, h->stream));
+  if (dtables) HIPCHECK(hipMemcpyAsync(D.d_tjv_dt, dtables, sizeof(double) * TAB_ROWS * n * ns, hipMemcpyHostToDevice, h->stream));
+  if (dslot) HIPCHECK(hipMemcpyAsync(D.d_tjv_ds, dslot, sizeof(double) * TS_NS * N * B, hipMemcpyHostToDevice, h->stream));
+  if (tjv_compute(h, dp ? D.d_tjv_dp : nullptr, dtables ? D.d_tjv_dt : nullptr, dslot ? D.d_tjv_ds : nullptr, tX ? D.d_tjv_tX : nullptr,
+                  tU ? D.d_tjv_tU : nullptr, who, sets))
+    return -1;
+  if (copy_out(h, D2H, tX, D.d_tjv_tX, (N + 1) * 8 * B) || copy_out(h, D2H, tU, D.d_tjv_tU, N * 2 * B) || copy_out(h, D2H, ok, D.d_sens_ok, B))
+    return -1;
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 // k_plant_sens' planes and the row-major staging of the host forms and, with `loop`, the closed loop's state: each on the first
 // request, with one synchronisation.
 int psn_prepare(ltompc_solver* h, const bool loop) {
@@ -805,6 +896,38 @@ int ltompc_get_jvp(ltompc_handle h, const double* dp, const double* dtheta, doub
     return -1;
   HIPCHECK(hipStreamSynchronize(h->stream));
   return 0;
+}
+
+int ltompc_jvp_tables_dev(ltompc_handle h, const double* dp_dev, const double* dtables_dev, const double* dslot_dev, double* tX_dev,
+                          double* tU_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  HIPCHECK(hipSetDevice(h->device));
+  if (tjv_compute(h, dp_dev, dtables_dev, dslot_dev, tX_dev, tU_dev, "ltompc_jvp_tables_dev")) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_jvp_tables(ltompc_handle h, const double* dp, const double* dtables, const double* dslot, double* tX, double* tU, int* ok) {
+  if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  return tjv_host(h, dp, dtables, dslot, tX, tU, ok, "ltompc_get_jvp_tables", false);
+}
+
+// The same two calls on a handle with per-instance table sets: dtables is [n_sets][4][n_table] and instance b
+// moves along the block of its set, set_of_instance[b]; dp, dslot and the outputs as above.
+int ltompc_jvp_table_sets_dev(ltompc_handle h, const double* dp_dev, const double* dtables_dev, const double* dslot_dev, double* tX_dev,
+                              double* tU_dev, int* ok_dev) {
+  if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  HIPCHECK(hipSetDevice(h->device));
+  if (tjv_compute(h, dp_dev, dtables_dev, dslot_dev, tX_dev, tU_dev, "ltompc_jvp_table_sets_dev", true)) return -1;
+  return copy_out(h, D2D, ok_dev, h->dv.d_sens_ok, h->B);
+}
+
+int ltompc_get_jvp_table_sets(ltompc_handle h, const double* dp, const double* dtables, const double* dslot, double* tX, double* tU, int* ok) {
+  if (!h) return fail("null handle");
+  RecScope on_record(h);  // (the selected record, if any, in the handle's place)
+  return tjv_host(h, dp, dtables, dslot, tX, tU, ok, "ltompc_get_jvp_table_sets", true);
 }
 
 int ltompc_plant_sensitivities_dev(ltompc_handle h, const double* x_dev, const double* u_dev, int n_sub, double* x_next_dev, double* dxn_dx_dev,

@@ -35,7 +35,10 @@
 //   table_sensitivity.h k_adj_sweep_tab, k_tab_cond, k_tab_scatter: the gradient of a loss of the predicted trajectory w.r.t. the knot
 //                 values of the track tables (ltompc_get_adjoint_tables): adjoint.h's recursion keeping its trajectory,
 //                 the per-slot contraction with the condensed columns of the ten look-up results, the scatter to the knots (lut_basis)
-//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the six headers above
+//   table_jvp.h   k_tabjvp_cond, k_jvp_sweep_tab: the product of those Jacobians w.r.t. the knot values with one direction
+//                 (ltompc_get_jvp_tables): the ten look-up tangents of every slot (given, or gathered with lut_basis),
+//                 their columns condensed into one stage vector, jvp.h's recursion on it
+//   deriv_passes.h (host, part of ltompc.hip only) the drivers and C entry points of the passes of the seven headers above
 //   warm_state.h  per-instance control of the warm start: k_load_x0_m / k_init_m / k_roll_mark_m / k_roll_init_m (the
 //                 start of a solve with a per-instance cold flag), k_ws_reset_* (ltompc_reset_instances), k_ws_guess (ltompc_set_guess),
 //                 k_ws_export / k_ws_import (the carried state of chosen instances <-> instance-major blobs, an LDS tile transpose)
@@ -70,6 +73,7 @@
 #include "jvp.h"
 #include "plant_sensitivity.h"
 #include "table_sensitivity.h"
+#include "table_jvp.h"
 #include "warm_state.h"
 #include "record.h"
 #include "policy.h"

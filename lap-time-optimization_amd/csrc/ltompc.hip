@@ -75,6 +75,11 @@ struct DerivState {
   WorkTS Wsts{}, *d_Wsts = nullptr;
   double* d_tab_gs = nullptr;
   int tab_gs_cap = 0;
+  // directional pass in the tables (table_jvp.h): the stage-vector planes, kff planes of its own, and the staging of the host form's
+  // directions (dtables: tjv_dt_cap blocks of 4 x n_table) and results
+  double *d_tjv_tq = nullptr, *d_tjv_jv = nullptr, *d_tjv_dp = nullptr, *d_tjv_dt = nullptr, *d_tjv_ds = nullptr, *d_tjv_tX = nullptr,
+         *d_tjv_tU = nullptr;
+  int tjv_dt_cap = 0;
   // feedback policy (policy.h): the staging of the host forms, gains (B x N x 16, B x N x 4) and x | v | u (B x 12)
   double *d_pol_K = nullptr, *d_pol_Kv = nullptr, *d_pol_io = nullptr;
 };

@@ -254,7 +254,7 @@ class BatchedMPC:
         return into if into is not None else SolveRecord(self, rec)
 
     def select_record(self, rec: "SolveRecord | None"):
-        """The derivative passes (sensitivities, param_sensitivities, adjoint, adjoint_tables, jvp and their _dev forms) run on
+        """The derivative passes (sensitivities, param_sensitivities, adjoint, adjoint_tables, jvp, jvp_tables and their _dev forms) run on
         `rec` from now on, bit for bit as right after the recorded solve; None: back to the live solve.  Everything else keeps
         working on the live handle.  The first pass after a change re-linearises and re-factorises (about one iteration)."""
         if rec is not None and (not isinstance(rec, SolveRecord) or rec._mpc is not self):
@@ -441,6 +441,49 @@ class BatchedMPC:
         (B,) int32; dtheta_ptr = 0 skips the parameter part of the pass."""
         check(lib().ltompc_jvp_dev(self._h, C.c_void_p(dp_ptr or None), C.c_void_p(dtheta_ptr or None), C.c_void_p(tX_ptr or None),
                                    C.c_void_p(tU_ptr or None), C.c_void_p(ok_ptr or None)))
+
+    # ---- directional sensitivities along a direction in the track tables (ltompc_get_jvp_tables, DESIGN.md §19) ---------------
+    def _jvp_tables(self, who, fn, n_blocks, dp, dtables, dslot):
+        B, N, n = self.B, self.N, self._tab.shape[1]
+        if dp is None and dtables is None and dslot is None:
+            raise ValueError(f"{who}: dp, dtables and dslot are all None (no direction)")
+        if dp is not None:
+            dp = _shaped(who, "dp", dp, (B, 10))
+        if dtables is not None:
+            dtables = _shaped(who, "dtables", dtables, (len(TABLE_ROW_NAMES), n) if n_blocks is None else (n_blocks, len(TABLE_ROW_NAMES), n))
+        if dslot is not None:
+            dslot = _shaped(who, "dslot", dslot, (B, N, len(TABLE_SLOT_NAMES)))
+        tX, tU, ok = np.empty((B, N + 1, NX)), np.empty((B, N, NU)), np.empty(B, dtype=np.int32)
+        check(fn(self._h, *(dptr(a) if a is not None else None for a in (dp, dtables, dslot)), dptr(tX), dptr(tU), iptr(ok)))
+        return dict(tX=tX, tU=tU, ok=ok != 0)
+
+    def jvp_tables(self, dp=None, dtables=None, dslot=None):
+        """Directional derivative of the last solve's predicted trajectory along a direction in the track tables, the forward
+        twin of adjoint_tables: dtables (4, n_table), one direction in the knot values of the rows TABLE_ROW_NAMES shared by
+        all instances, and / or dslot (B,N,10), the tangents of the ten look-up results of every interval (TABLE_SLOT_NAMES,
+        the forward twin of slot_grad), summed; dp (B,10: x0[0..7], u_prev[0..1]) is added in the same sweep.  None: zeros;
+        not all three.  A direction in theta is jvp()'s: the map is linear, add the two results.
+
+        Returns tX (B,N+1,8; block 0 is dp[:, :8] or 0), tU (B,N,2), ok (B,) bool (the same as sensitivities()' ok).  Where
+        ok is False every output of the instance is 0.  Deterministic (no atomic adds)."""
+        return self._jvp_tables("jvp_tables", lib().ltompc_get_jvp_tables, None, dp, dtables, dslot)
+
+    def jvp_tables_dev(self, dp_ptr: int = 0, dtables_ptr: int = 0, dslot_ptr: int = 0, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
+        """Enqueue the directional pass in the tables of the last solve on the handle's stream: directions from device arrays
+        (B,10) / (4,n_table) / (B,N,10) of doubles (0: zeros; not all three, NOT checked for finiteness), results into device
+        arrays (B,N+1,8) / (B,N,2) doubles / (B,) int32 (0: not wanted)."""
+        check(lib().ltompc_jvp_tables_dev(self._h, *(C.c_void_p(a or None) for a in (dp_ptr, dtables_ptr, dslot_ptr, tX_ptr, tU_ptr, ok_ptr))))
+
+    def jvp_table_sets(self, dp=None, dtables=None, dslot=None):
+        """jvp_tables on a handle with table sets: dtables is (n_sets, 4, n_table), one direction per set, and instance b moves
+        along the block of its own set, on that set's rows; dp, dslot and the results as there."""
+        if not self.n_table_sets:
+            raise ValueError("jvp_table_sets: the handle has no table sets (set_table_sets); its directional pass in the tables is jvp_tables()")
+        return self._jvp_tables("jvp_table_sets", lib().ltompc_get_jvp_table_sets, self.n_table_sets, dp, dtables, dslot)
+
+    def jvp_table_sets_dev(self, dp_ptr: int = 0, dtables_ptr: int = 0, dslot_ptr: int = 0, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
+        """jvp_tables_dev on a handle with table sets: dtables is (n_sets,4,n_table) doubles."""
+        check(lib().ltompc_jvp_table_sets_dev(self._h, *(C.c_void_p(a or None) for a in (dp_ptr, dtables_ptr, dslot_ptr, tX_ptr, tU_ptr, ok_ptr))))
 
     def prediction_dev(self, X_ptr: int = 0, U_ptr: int = 0):
         """Enqueue a copy of the last solve's prediction into device arrays (B,N+1,8) / (B,N,2) of doubles in the caller's
@@ -1435,6 +1478,38 @@ class SplitMPC:
         for p, (lo, hi) in zip(self.parts, self.bounds):
             p.jvp_dev(dp_ptr + 8 * 10 * lo if dp_ptr else 0, dtheta_ptr + 8 * NTHETA * lo if dtheta_ptr else 0,
                       tX_ptr + 8 * (N + 1) * NX * lo if tX_ptr else 0, tU_ptr + 8 * N * NU * lo if tU_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def _jvp_tables_parts(self, name, dp, dtables, dslot):
+        dp = None if dp is None else np.asarray(dp, dtype=np.float64)
+        dslot = None if dslot is None else np.asarray(dslot, dtype=np.float64)
+        r = [getattr(p, name)(None if dp is None else dp[lo:hi], dtables, None if dslot is None else dslot[lo:hi])
+             for p, (lo, hi) in zip(self.parts, self.bounds)]
+        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+
+    def _jvp_tables_parts_dev(self, name, dp_ptr, dtables_ptr, dslot_ptr, tX_ptr, tU_ptr, ok_ptr):
+        N = self.N
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            getattr(p, name)(dp_ptr + 8 * 10 * lo if dp_ptr else 0, dtables_ptr, dslot_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if dslot_ptr else 0,
+                             tX_ptr + 8 * (N + 1) * NX * lo if tX_ptr else 0, tU_ptr + 8 * N * NU * lo if tU_ptr else 0,
+                             ok_ptr + 4 * lo if ok_ptr else 0)
+
+    def jvp_tables(self, dp=None, dtables=None, dslot=None):
+        """BatchedMPC.jvp_tables of every part: dtables to every part, dp and dslot by the part's rows, the results stitched in
+        the caller's order (they are per instance: nothing is summed over the parts)."""
+        return self._jvp_tables_parts("jvp_tables", dp, dtables, dslot)
+
+    def jvp_tables_dev(self, dp_ptr: int = 0, dtables_ptr: int = 0, dslot_ptr: int = 0, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.jvp_tables_dev of every part on the same (4,n_table) direction and its rows of (B,10) / (B,N,10) into its
+        rows of (B,N+1,8) / (B,N,2) doubles / (B,) int32, each on its part's stream."""
+        self._jvp_tables_parts_dev("jvp_tables_dev", dp_ptr, dtables_ptr, dslot_ptr, tX_ptr, tU_ptr, ok_ptr)
+
+    def jvp_table_sets(self, dp=None, dtables=None, dslot=None):
+        """BatchedMPC.jvp_table_sets of every part, as jvp_tables: the (n_sets,4,n_table) direction to every part."""
+        return self._jvp_tables_parts("jvp_table_sets", dp, dtables, dslot)
+
+    def jvp_table_sets_dev(self, dp_ptr: int = 0, dtables_ptr: int = 0, dslot_ptr: int = 0, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
+        """BatchedMPC.jvp_table_sets_dev of every part, as jvp_tables_dev."""
+        self._jvp_tables_parts_dev("jvp_table_sets_dev", dp_ptr, dtables_ptr, dslot_ptr, tX_ptr, tU_ptr, ok_ptr)
 
     def set_u_prev(self, u_prev):
         """BatchedMPC.set_u_prev with the rows split across the parts."""
