@@ -2,6 +2,8 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
+from typing import NamedTuple
 
 import numpy as np
 
@@ -10,6 +12,21 @@ from ._lib import LOOP_NAMES, NLOOP, NTHETA, NX, NU, TABLE_ROW_NAMES, TABLE_SLOT
 from .tables import TrackTables
 
 KERNEL_CLASSES = ("eval", "riccati", "expand", "linesearch", "pick", "update", "riccati1", "step1")  # include/ltompc.h
+NP = NX + NU  # columns of a derivative w.r.t. p = (x0[0..7], u_prev[0..1])
+NSLOT = len(TABLE_SLOT_NAMES)  # table look-up results of one interval
+INT32_ROWS = ("flag", "i_log")  # the names of row_shape whose elements are int32; every other one holds doubles
+
+
+def row_shape(name, N=0, n=0):
+    """The shape of one instance's row of the (B, ...) array `name` of the C ABI (include/ltompc.h), for horizon N and, for a log,
+    n ticks.  The one place that spells them: BatchedMPC allocates and checks by it, SplitMPC offsets device pointers by it."""
+    return {"x": (NX,), "u": (NU,), "X": (N + 1, NX), "U": (N, NU), "C": (N, NX), "p": (NP,), "theta": (NTHETA,),
+            "du0_dp": (NU, NP), "dX_dp": (N + 1, NX, NP), "dU_dp": (N, NU, NP),
+            "du0_dtheta": (NU, NTHETA), "dX_dtheta": (N + 1, NX, NTHETA), "dU_dtheta": (N, NU, NTHETA),
+            "slot": (N, NSLOT), "K": (N, NU, NX), "Kv": (N, NU, NU),
+            "plant_dx": (NX, NX), "plant_du": (NX, NU), "plant_dtheta": (NX, NTHETA), "loop_dx": (NX, NLOOP), "loop_du": (NU, NLOOP),
+            "u_log": (n, NU), "x_log": (n, NX), "i_log": (n,),  # (policy_run_dev and rollout_dev logs; status and iterations)
+            "flag": ()}[name]  # (ok, a mask, the table-set index)
 
 
 class SolveRecord:
@@ -185,12 +202,11 @@ class BatchedMPC:
         states (None: x_k + (x_{k+1} - x_k) / 3, the Radau point at tau = 1/3), u_prev (B,2) or None (= 0).  The guess stands
         in for a previous solution that did not converge (status MAX_ITER, multipliers 0): the next solve warm-starts from it
         under the handle's warm-start options.  ltompc_set_guess."""
-        B, N = self.B, self.N
-        m = _mask(mask, B)
-        X = _shaped("set_guess", "X", X, (B, N + 1, NX))
-        U = _shaped("set_guess", "U", U, (B, N, NU))
-        Cc = guess_collocation(X) if C is None else _shaped("set_guess", "C", C, (B, N, NX))
-        up = None if u_prev is None else _shaped("set_guess", "u_prev", u_prev, (B, NU))
+        m = _mask(mask, self.B)
+        X = _shaped("set_guess", "X", X, self._shape("X"))
+        U = _shaped("set_guess", "U", U, self._shape("U"))
+        Cc = guess_collocation(X) if C is None else _shaped("set_guess", "C", C, self._shape("C"))
+        up = _shaped_or_none("set_guess", "u_prev", u_prev, self._shape("u"))
         check(lib().ltompc_set_guess(self._h, iptr(m), dptr(X), dptr(Cc), dptr(U), dptr(up) if up is not None else None))
         self._instances_changed(m != 0, 0.0 if up is None else up[m != 0])
 
@@ -300,10 +316,9 @@ class BatchedMPC:
 
         Returns du0_dx0 (B,2,8), du0_duprev (B,2,2), ok (B,) bool, margin (B,) and, with trajectory=True, dX (B,N+1,8,10) and
         dU (B,N,2,10) (columns: x0[0..7], u_prev[0..1]).  Where ok is False every output of the instance is 0."""
-        B, N = self.B, self.N
-        du0, ok, margin = np.empty((B, NU, 10)), np.empty(B, dtype=np.int32), np.empty(B)
-        dX = np.empty((B, N + 1, NX, 10)) if trajectory else None
-        dU = np.empty((B, N, NU, 10)) if trajectory else None
+        du0, ok, margin = self._empty("du0_dp"), self._empty("flag"), np.empty(self.B)
+        dX = self._empty("dX_dp") if trajectory else None
+        dU = self._empty("dU_dp") if trajectory else None
         check(lib().ltompc_get_sensitivities(self._h, dptr(du0), dptr(dX) if trajectory else None, dptr(dU) if trajectory else None,
                                              iptr(ok), dptr(margin)))
         out = dict(du0_dx0=du0[:, :, :NX].copy(), du0_duprev=du0[:, :, NX:].copy(), ok=ok != 0, margin=margin)
@@ -326,10 +341,9 @@ class BatchedMPC:
 
         Returns du0_dtheta (B,2,16), names (the 16 column names), ok (B,) bool (the same as sensitivities()' ok) and, with
         trajectory=True, dX (B,N+1,8,16, block 0 is 0) and dU (B,N,2,16).  Where ok is False every output of the instance is 0."""
-        B, N = self.B, self.N
-        du0, ok = np.empty((B, NU, NTHETA)), np.empty(B, dtype=np.int32)
-        dX = np.empty((B, N + 1, NX, NTHETA)) if trajectory else None
-        dU = np.empty((B, N, NU, NTHETA)) if trajectory else None
+        du0, ok = self._empty("du0_dtheta"), self._empty("flag")
+        dX = self._empty("dX_dtheta") if trajectory else None
+        dU = self._empty("dU_dtheta") if trajectory else None
         check(lib().ltompc_get_param_sensitivities(self._h, dptr(du0), dptr(dX) if trajectory else None,
                                                    dptr(dU) if trajectory else None, iptr(ok)))
         out = dict(du0_dtheta=du0, names=THETA_NAMES, ok=ok != 0)
@@ -351,17 +365,9 @@ class BatchedMPC:
 
         Returns grad_x0 (B,8), grad_uprev (B,2), grad_theta (B,16, only with theta=True), names, ok (B,) bool (the same as
         sensitivities()' ok).  Where ok is False every output of the instance is 0."""
-        B, N = self.B, self.N
-        if gX is not None:
-            gX = np.ascontiguousarray(gX, dtype=np.float64)
-            if gX.shape != (B, N + 1, NX):
-                raise ValueError(f"adjoint: gX must have shape {(B, N + 1, NX)}, got {gX.shape}")
-        if gU is not None:
-            gU = np.ascontiguousarray(gU, dtype=np.float64)
-            if gU.shape != (B, N, NU):
-                raise ValueError(f"adjoint: gU must have shape {(B, N, NU)}, got {gU.shape}")
-        gp, ok = np.empty((B, 10)), np.empty(B, dtype=np.int32)
-        gth = np.empty((B, NTHETA)) if theta else None
+        gX, gU = _shaped_or_none("adjoint", "gX", gX, self._shape("X")), _shaped_or_none("adjoint", "gU", gU, self._shape("U"))
+        gp, ok = self._empty("p"), self._empty("flag")
+        gth = self._empty("theta") if theta else None
         check(lib().ltompc_get_adjoint(self._h, dptr(gX) if gX is not None else None, dptr(gU) if gU is not None else None,
                                        dptr(gp), dptr(gth) if theta else None, iptr(ok)))
         out = dict(grad_x0=gp[:, :NX].copy(), grad_uprev=gp[:, NX:].copy(), names=THETA_NAMES, ok=ok != 0)
@@ -386,20 +392,15 @@ class BatchedMPC:
         contributes 0) and, with slots=True, slot_grad (B,N,10): the gradient w.r.t. the ten look-up results of every interval
         (slot_names = TABLE_SLOT_NAMES), which is deterministic and what a table parametrisation of the caller's own chains
         through.  The last bits of grad_tables can differ between two calls (atomic adds over the instances)."""
-        B, N = self.B, self.N
-        if gX is not None:
-            gX = np.ascontiguousarray(gX, dtype=np.float64)
-            if gX.shape != (B, N + 1, NX):
-                raise ValueError(f"adjoint_tables: gX must have shape {(B, N + 1, NX)}, got {gX.shape}")
-        if gU is not None:
-            gU = np.ascontiguousarray(gU, dtype=np.float64)
-            if gU.shape != (B, N, NU):
-                raise ValueError(f"adjoint_tables: gU must have shape {(B, N, NU)}, got {gU.shape}")
-        gt, ok = np.empty((len(TABLE_ROW_NAMES), self._tab.shape[1])), np.empty(B, dtype=np.int32)
-        sg = np.empty((B, N, len(TABLE_SLOT_NAMES))) if slots else None
-        check(lib().ltompc_get_adjoint_tables(self._h, dptr(gX) if gX is not None else None, dptr(gU) if gU is not None else None,
-                                              dptr(gt), dptr(sg) if slots else None, iptr(ok)))
-        out = dict(grad_tables=gt, names=TABLE_ROW_NAMES, ok=ok != 0)
+        return self._adjoint_tables("adjoint_tables", lib().ltompc_get_adjoint_tables, "grad_tables", (), gX, gU, slots)
+
+    def _adjoint_tables(self, who, fn, key, blocks, gX, gU, slots):
+        """adjoint_tables and adjoint_table_sets: the gradient `key` has the leading shape `blocks` (one block per table set)."""
+        gX, gU = _shaped_or_none(who, "gX", gX, self._shape("X")), _shaped_or_none(who, "gU", gU, self._shape("U"))
+        g, ok = np.empty(blocks + (len(TABLE_ROW_NAMES), self._tab.shape[1])), self._empty("flag")
+        sg = self._empty("slot") if slots else None
+        check(fn(self._h, *(dptr(a) if a is not None else None for a in (gX, gU)), dptr(g), dptr(sg) if slots else None, iptr(ok)))
+        out = {key: g, "names": TABLE_ROW_NAMES, "ok": ok != 0}
         if slots:
             out.update(slot_grad=sg, slot_names=TABLE_SLOT_NAMES)
         return out
@@ -421,18 +422,9 @@ class BatchedMPC:
 
         Returns tX (B,N+1,8; block 0 is dp[:, :8]), tU (B,N,2), ok (B,) bool (the same as sensitivities()' ok).  Where ok is
         False every output of the instance is 0."""
-        B, N = self.B, self.N
-        if dp is not None:
-            dp = np.ascontiguousarray(dp, dtype=np.float64)
-            if dp.shape != (B, 10):
-                raise ValueError(f"jvp: dp must have shape {(B, 10)}, got {dp.shape}")
-        if dtheta is not None:
-            dtheta = np.ascontiguousarray(dtheta, dtype=np.float64)
-            if dtheta.shape != (B, NTHETA):
-                raise ValueError(f"jvp: dtheta must have shape {(B, NTHETA)}, got {dtheta.shape}")
-        tX, tU, ok = np.empty((B, N + 1, NX)), np.empty((B, N, NU)), np.empty(B, dtype=np.int32)
-        check(lib().ltompc_get_jvp(self._h, dptr(dp) if dp is not None else None, dptr(dtheta) if dtheta is not None else None,
-                                   dptr(tX), dptr(tU), iptr(ok)))
+        dp, dtheta = _shaped_or_none("jvp", "dp", dp, self._shape("p")), _shaped_or_none("jvp", "dtheta", dtheta, self._shape("theta"))
+        tX, tU, ok = self._empty("X"), self._empty("U"), self._empty("flag")
+        check(lib().ltompc_get_jvp(self._h, *(dptr(a) if a is not None else None for a in (dp, dtheta)), dptr(tX), dptr(tU), iptr(ok)))
         return dict(tX=tX, tU=tU, ok=ok != 0)
 
     def jvp_dev(self, dp_ptr: int, dtheta_ptr: int, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
@@ -444,16 +436,13 @@ class BatchedMPC:
 
     # ---- directional sensitivities along a direction in the track tables (ltompc_get_jvp_tables) ---------------
     def _jvp_tables(self, who, fn, n_blocks, dp, dtables, dslot):
-        B, N, n = self.B, self.N, self._tab.shape[1]
+        n = self._tab.shape[1]
         if dp is None and dtables is None and dslot is None:
             raise ValueError(f"{who}: dp, dtables and dslot are all None (no direction)")
-        if dp is not None:
-            dp = _shaped(who, "dp", dp, (B, 10))
-        if dtables is not None:
-            dtables = _shaped(who, "dtables", dtables, (len(TABLE_ROW_NAMES), n) if n_blocks is None else (n_blocks, len(TABLE_ROW_NAMES), n))
-        if dslot is not None:
-            dslot = _shaped(who, "dslot", dslot, (B, N, len(TABLE_SLOT_NAMES)))
-        tX, tU, ok = np.empty((B, N + 1, NX)), np.empty((B, N, NU)), np.empty(B, dtype=np.int32)
+        dp = _shaped_or_none(who, "dp", dp, self._shape("p"))
+        dtables = _shaped_or_none(who, "dtables", dtables, (len(TABLE_ROW_NAMES), n) if n_blocks is None else (n_blocks, len(TABLE_ROW_NAMES), n))
+        dslot = _shaped_or_none(who, "dslot", dslot, self._shape("slot"))
+        tX, tU, ok = self._empty("X"), self._empty("U"), self._empty("flag")
         check(fn(self._h, *(dptr(a) if a is not None else None for a in (dp, dtables, dslot)), dptr(tX), dptr(tU), iptr(ok)))
         return dict(tX=tX, tU=tU, ok=ok != 0)
 
@@ -498,8 +487,7 @@ class BatchedMPC:
         Returns K (B,N,2,8), Kv (B,N,2,2) - the stage gains of the delta_w = 0 factorisation at the final iterate, K[:, 0] =
         du0_dx0 and Kv[:, 0] = du0_duprev of sensitivities() bit for bit - and ok (B,) bool (the same as sensitivities()' ok).
         Where ok is False the gains are 0: the policy is the open-loop plan."""
-        B, N = self.B, self.N
-        K, Kv, ok = np.empty((B, N, NU, NX)), np.empty((B, N, NU, NU)), np.empty(B, dtype=np.int32)
+        K, Kv, ok = self._empty("K"), self._empty("Kv"), self._empty("flag")
         check(lib().ltompc_get_policy(self._h, dptr(K), dptr(Kv), iptr(ok)))
         return dict(K=K, Kv=Kv, ok=ok != 0)
 
@@ -512,8 +500,8 @@ class BatchedMPC:
         saturates u at the bounds of delta and T one t_step ahead, then at the input bounds (include/ltompc.h).  A non-finite x
         or v is refused."""
         x = self._x(x)
-        vv = None if v is None else _shaped("policy_step", "v", v, (self.B, NU))
-        u = np.empty((self.B, NU))
+        vv = _shaped_or_none("policy_step", "v", v, self._shape("u"))
+        u = self._empty("u")
         check(lib().ltompc_policy_step(self._h, int(k), dptr(x), dptr(vv) if vv is not None else None, int(bool(clip)), dptr(u)))
         return u
 
@@ -543,8 +531,8 @@ class BatchedMPC:
         if k0 < 0 or n < 1 or k0 + n > self.N:
             raise ValueError(f"policy_run: need 0 <= k0, 1 <= n and k0 + n <= {self.N}, got k0 = {k0}, n = {n}")
         x = self._x(x)
-        v = None if v is None else _shaped("policy_run", "v", v, (self.B, NU))
-        ul, xl = np.empty((self.B, n, NU)), np.empty((self.B, n, NX))
+        v = _shaped_or_none("policy_run", "v", v, self._shape("u"))
+        ul, xl = self._empty("u_log", n), self._empty("x_log", n)
         for j in range(n):
             v = self.policy_step(k0 + j, x, v, clip)
             x = self.plant_step(x, v, n_sub)
@@ -557,8 +545,8 @@ class BatchedMPC:
         plant_step), dx (B,8,8), du (B,8,2) and, with theta=True, dtheta (B,8,16; columns THETA_NAMES, the cost columns 0);
         names.  With per-instance rows: at the rows in effect, as plant_step."""
         x, u = self._x(x), np.ascontiguousarray(np.asarray(u, float).reshape(self.B, NU))
-        xn, dx, du = np.empty_like(x), np.empty((self.B, NX, NX)), np.empty((self.B, NX, NU))
-        dth = np.empty((self.B, NX, NTHETA)) if theta else None
+        xn, dx, du = np.empty_like(x), self._empty("plant_dx"), self._empty("plant_du")
+        dth = self._empty("plant_dtheta") if theta else None
         check(lib().ltompc_plant_sensitivities(self._h, dptr(x), dptr(u), int(n_sub), dptr(xn), dptr(dx), dptr(du),
                                                dptr(dth) if theta else None))
         out = dict(x_next=xn, dx=dx, du=du, names=THETA_NAMES)
@@ -593,8 +581,8 @@ class BatchedMPC:
     def loop_sensitivities(self):
         """dx (B,8,24) = dx_t/dq and du (B,2,24) = du_{t-1}/dq after the ticks so far, columns names = LOOP_NAMES (x_init[0..7],
         then THETA_NAMES); ok (B,) bool, ticks (B,) (the ticks accumulated while ok).  Where ok is False dx and du are 0."""
-        dx, du = np.empty((self.B, NX, NLOOP)), np.empty((self.B, NU, NLOOP))
-        ok, ticks = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        dx, du = self._empty("loop_dx"), self._empty("loop_du")
+        ok, ticks = self._empty("flag"), self._empty("flag")
         check(lib().ltompc_get_loop_sensitivities(self._h, dptr(dx), dptr(du), iptr(ok), iptr(ticks)))
         return dict(dx=dx, du=du, ok=ok != 0, ticks=ticks, names=LOOP_NAMES)
 
@@ -702,21 +690,9 @@ class BatchedMPC:
     def adjoint_table_sets(self, gX=None, gU=None, slots: bool = False):
         """adjoint_tables on a handle with table sets: grad_sets (n_sets, 4, n_table), block g summed over the ok instances of
         set g (zeros for a set without instances), in place of grad_tables; names, ok and, with slots=True, slot_grad as there."""
-        B, N = self.B, self.N
         if not self.n_table_sets:
             raise ValueError("adjoint_table_sets: the handle has no table sets (set_table_sets); its table gradient is adjoint_tables()")
-        if gX is not None:
-            gX = _shaped("adjoint_table_sets", "gX", gX, (B, N + 1, NX))
-        if gU is not None:
-            gU = _shaped("adjoint_table_sets", "gU", gU, (B, N, NU))
-        gs, ok = np.empty((self.n_table_sets, len(TABLE_ROW_NAMES), self._tab.shape[1])), np.empty(B, dtype=np.int32)
-        sg = np.empty((B, N, len(TABLE_SLOT_NAMES))) if slots else None
-        check(lib().ltompc_get_adjoint_table_sets(self._h, dptr(gX) if gX is not None else None, dptr(gU) if gU is not None else None,
-                                                  dptr(gs), dptr(sg) if slots else None, iptr(ok)))
-        out = dict(grad_sets=gs, names=TABLE_ROW_NAMES, ok=ok != 0)
-        if slots:
-            out.update(slot_grad=sg, slot_names=TABLE_SLOT_NAMES)
-        return out
+        return self._adjoint_tables("adjoint_table_sets", lib().ltompc_get_adjoint_table_sets, "grad_sets", (self.n_table_sets,), gX, gU, slots)
 
     def adjoint_table_sets_dev(self, gX_ptr: int, gU_ptr: int, grad_sets_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0, add: bool = False):
         """adjoint_tables_dev on a handle with table sets: grad_sets (n_sets,4,n_table) doubles in place of grad_tables
@@ -804,13 +780,13 @@ class BatchedMPC:
 
     # ---- results --------------------------------------------------------------------------------
     def prediction(self):
-        X, U = np.empty((self.B, self.N + 1, NX)), np.empty((self.B, self.N, NU))
+        X, U = self._empty("X"), self._empty("U")
         check(lib().ltompc_get_prediction(self._h, dptr(X), dptr(U)))
         return X, U
 
     def iterate(self):
-        X, U = np.empty((self.B, self.N + 1, NX)), np.empty((self.B, self.N, NU))
-        Cc, L1, L2 = (np.empty((self.B, self.N, NX)) for _ in range(3))
+        X, U = self._empty("X"), self._empty("U")
+        Cc, L1, L2 = (self._empty("C") for _ in range(3))
         check(lib().ltompc_get_iterate(self._h, dptr(X), dptr(Cc), dptr(U), dptr(L1), dptr(L2)))
         ni = C.c_int()
         check(lib().ltompc_get_ineq(self._h, None, None, C.byref(ni)))
@@ -939,6 +915,13 @@ class BatchedMPC:
         check(lib().ltompc_test_ellipse(self._h, n, dptr(x), dptr(v), dptr(g), dptr(H)))
         return v, g, H
 
+    def _shape(self, name, n=0):
+        """(B,) + row_shape: the whole-batch shape of the array `name`."""
+        return (self.B,) + row_shape(name, self.N, n)
+
+    def _empty(self, name, n=0):
+        return np.empty(self._shape(name, n), dtype=np.int32 if name in INT32_ROWS else np.float64)
+
     def _x(self, x0):
         x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(-1, NX))
         if x0.shape[0] != self.B:
@@ -981,6 +964,11 @@ def _shaped(who, name, a, shape):
     if a.shape != shape:
         raise ValueError(f"{who}: {name} must have shape {shape}, got {a.shape}")
     return a
+
+
+def _shaped_or_none(who, name, a, shape):
+    """_shaped for an optional argument: None (not given) stays None."""
+    return None if a is None else _shaped(who, name, a, shape)
 
 
 _DEV_ROWS = object()  # BatchedMPC._theta_rows after set_theta_dev: the rows are in device memory only
@@ -1057,6 +1045,36 @@ def _set_index(index, B, n_sets):
     return np.array(ix, dtype=np.int32, order="C", copy=True)
 
 
+class _Rows(NamedTuple):
+    """An argument of SplitMPC._forward_dev: the device pointer of a (B, ...) array of which every part gets its own rows (0: no
+    array, for every part); name and n as in row_shape."""
+    ptr: int
+    name: str
+    n: int = 0
+
+
+def _f64(a):
+    """A per-instance host input as float64, for slicing by rows; None (not given) stays None."""
+    return None if a is None else np.asarray(a, dtype=np.float64)
+
+
+def _stitch(r, first=(), summed=()):
+    """One dict from the result dicts r of the parts: a key in `first` is the same for all parts and taken from the first one; a
+    key in `summed` is added up in part order, into a copy of the first part's array; every other one holds one row per
+    instance and is concatenated in part order, which is the caller's."""
+    out = {}
+    for k in r[0]:
+        if k in first:
+            out[k] = r[0][k]
+        elif k in summed:
+            out[k] = r[0][k].copy()
+            for q in r[1:]:
+                out[k] += q[k]
+        else:
+            out[k] = np.concatenate([q[k] for q in r])
+    return out
+
+
 class SplitMPC:
     """The batch as `n_parts` handles of batch / n_parts instances, each on its own HIP stream and driven by its own host thread
     (ctypes releases the GIL during a call).  Instances are independent NLPs, so the parts need not tick together: while one
@@ -1099,6 +1117,33 @@ class SplitMPC:
         """fn(part, lo, hi) on every part, each in its own host thread; returns the results in part order."""
         futs = [self._pool.submit(fn, p, lo, hi) for p, (lo, hi) in zip(self.parts, self.bounds)]
         return [f.result() for f in futs]
+
+    def _forward_dev(self, method, *args, sum_into=None):
+        """BatchedMPC.`method` on every part, in part order and in the caller's thread; each part enqueues on its own stream.  A
+        _Rows argument is advanced to the part's first row (a 0 pointer stays 0); any other argument - the pointer of an array
+        that all parts share, a plain value - reaches every part as it is.  This is where the class offsets pointers (the timed
+        loop's set_initial_guess_dev, make_step_dev, run_ticks and rollout_dev apart).
+        sum_into: the pointer of an array that the parts add up in (adjoint_tables_dev).  The first part overwrites it, every
+        later one is called with add=True, after the part before it has finished (the handle is synchronised in between, so the
+        sum is the same from call to call up to each part's own atomic order); 0: no such array, nothing to wait for."""
+        for i, (p, (lo, hi)) in enumerate(zip(self.parts, self.bounds)):
+            def at(a):
+                item = 4 if a.name in INT32_ROWS else 8
+                return a.ptr + item * math.prod(row_shape(a.name, self.N, a.n)) * lo if a.ptr else 0
+            mine = [at(a) if isinstance(a, _Rows) else a for a in args]
+            if sum_into is None:
+                getattr(p, method)(*mine)
+            else:
+                if i and sum_into:
+                    self.parts[i - 1].synchronize()
+                getattr(p, method)(*mine, add=i > 0)
+
+    _shape = BatchedMPC._shape  # (the whole-batch shapes of the checks made before any part is touched)
+
+    def _rows_of(self, *arrays):
+        """(part, its rows of every array) for every part in order; an array that is None (not given) stays None."""
+        for p, (lo, hi) in zip(self.parts, self.bounds):
+            yield (p, *(None if a is None else a[lo:hi] for a in arrays))
 
     def set_initial_guess_dev(self, x0_ptr: int):
         self._each(lambda p, lo, hi: (p.set_initial_guess_dev(x0_ptr + 8 * NX * lo), p.synchronize()))
@@ -1204,12 +1249,10 @@ class SplitMPC:
         return sum(p.solver_status_counts() for p in self.parts)
 
     def stats(self):
-        r = [p.stats() for p in self.parts]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        return _stitch([p.stats() for p in self.parts])
 
     def iterate(self):
-        r = [p.iterate() for p in self.parts]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        return _stitch([p.iterate() for p in self.parts])
 
     # ---- per-instance control of the warm start: masks and global indices split across the parts, parts with nothing to do skipped
     def reset(self, mask, x0):
@@ -1220,35 +1263,30 @@ class SplitMPC:
             raise ValueError(f"reset: expected {self.B} states of dimension {NX}, got array of shape {x0.shape}")
         if not np.isfinite(x0[m != 0]).all():  # (the whole batch checked first: a bad row changes no part)
             raise ValueError("reset: non-finite x0 in a masked row")
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            if m[lo:hi].any():
-                p.reset(m[lo:hi], x0[lo:hi])
+        for p, mp, xp in self._rows_of(m, x0):
+            if mp.any():
+                p.reset(mp, xp)
 
     def reset_dev(self, mask_ptr: int, x0_ptr: int):
         """BatchedMPC.reset_dev of every part on its rows of (B,) int32 / (B,8) doubles, each on its part's stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.reset_dev(mask_ptr + 4 * lo, x0_ptr + 8 * NX * lo)
+        self._forward_dev("reset_dev", _Rows(mask_ptr, "flag"), _Rows(x0_ptr, "x"))
 
     def set_guess(self, mask, X, U, C=None, u_prev=None):
         """BatchedMPC.set_guess with the rows split across the parts."""
-        B, N = self.B, self.N
-        m = _mask(mask, B)
-        X, U = _shaped("set_guess", "X", X, (B, N + 1, NX)), _shaped("set_guess", "U", U, (B, N, NU))
-        Cc = guess_collocation(X) if C is None else _shaped("set_guess", "C", C, (B, N, NX))
-        up = None if u_prev is None else _shaped("set_guess", "u_prev", u_prev, (B, NU))
+        m = _mask(mask, self.B)
+        X, U = _shaped("set_guess", "X", X, self._shape("X")), _shaped("set_guess", "U", U, self._shape("U"))
+        Cc = guess_collocation(X) if C is None else _shaped("set_guess", "C", C, self._shape("C"))
+        up = _shaped_or_none("set_guess", "u_prev", u_prev, self._shape("u"))
         on = m != 0
         if not (np.isfinite(X[on]).all() and np.isfinite(U[on]).all() and np.isfinite(Cc[on]).all() and (up is None or np.isfinite(up[on]).all())):
             raise ValueError("set_guess: non-finite entry in a masked row")  # (checked first: a bad row changes no part)
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            if m[lo:hi].any():
-                p.set_guess(m[lo:hi], X[lo:hi], U[lo:hi], Cc[lo:hi], None if up is None else up[lo:hi])
+        for p, mp, *guess in self._rows_of(m, X, U, Cc, up):
+            if mp.any():
+                p.set_guess(mp, *guess)
 
     def set_guess_dev(self, mask_ptr: int, X_ptr: int, C_ptr: int, U_ptr: int, u_prev_ptr: int = 0):
         """BatchedMPC.set_guess_dev of every part on its rows, each on its part's stream."""
-        N = self.N
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.set_guess_dev(mask_ptr + 4 * lo, X_ptr + 8 * (N + 1) * NX * lo, C_ptr + 8 * N * NX * lo, U_ptr + 8 * N * NU * lo,
-                            u_prev_ptr + 8 * NU * lo if u_prev_ptr else 0)
+        self._forward_dev("set_guess_dev", _Rows(mask_ptr, "flag"), _Rows(X_ptr, "X"), _Rows(C_ptr, "C"), _Rows(U_ptr, "U"), _Rows(u_prev_ptr, "u"))
 
     @property
     def warm_state_size(self) -> int:
@@ -1284,8 +1322,8 @@ class SplitMPC:
             self._each(lambda p, lo, hi: p.set_theta(None))
             return
         rows = _theta_rows(theta, self.B, self.parts[0].theta())  # (the whole batch checked first: a bad row changes no part)
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.set_theta(rows[lo:hi])
+        for p, mine in self._rows_of(rows):
+            p.set_theta(mine)
 
     def instance_theta(self):
         return np.concatenate([p.instance_theta() for p in self.parts])
@@ -1325,14 +1363,13 @@ class SplitMPC:
             raise ValueError("set_table_sets: values=None keeps the sets in effect, and there are none")
         if index is not None:
             index = _set_index(index, self.B, n_sets)
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.set_table_sets(values, None if index is None else index[lo:hi])
+        for p, mine in self._rows_of(index):
+            p.set_table_sets(values, mine)
 
     def set_table_sets_dev(self, n_sets: int, values_ptr: int = 0, index_ptr: int = 0):
         """BatchedMPC.set_table_sets_dev on every part: each copies the same values and its rows of the (B,) int32 index on its
         own stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.set_table_sets_dev(n_sets, values_ptr, index_ptr + 4 * lo if index_ptr else 0)
+        self._forward_dev("set_table_sets_dev", n_sets, values_ptr, _Rows(index_ptr, "flag"))
 
     def table_sets(self):
         """The sets in effect: the values of the first part (every part holds the same ones), the index stitched by rows."""
@@ -1342,29 +1379,14 @@ class SplitMPC:
     def adjoint_table_sets(self, gX=None, gU=None, slots: bool = False):
         """BatchedMPC.adjoint_table_sets of every part with its rows of the cotangents: grad_sets summed over the parts in part
         order (on the host), slot_grad and ok stitched in the caller's order."""
-        gX = None if gX is None else np.asarray(gX, dtype=np.float64)
-        gU = None if gU is None else np.asarray(gU, dtype=np.float64)
-        r = [p.adjoint_table_sets(None if gX is None else gX[lo:hi], None if gU is None else gU[lo:hi], slots)
-             for p, (lo, hi) in zip(self.parts, self.bounds)]
-        out = dict(r[0], ok=np.concatenate([q["ok"] for q in r]))
-        gs = r[0]["grad_sets"].copy()
-        for q in r[1:]:
-            gs += q["grad_sets"]
-        out["grad_sets"] = gs
-        if slots:
-            out["slot_grad"] = np.concatenate([q["slot_grad"] for q in r])
-        return out
+        r = [p.adjoint_table_sets(gXp, gUp, slots) for p, gXp, gUp in self._rows_of(_f64(gX), _f64(gU))]
+        return _stitch(r, first=("names", "slot_names"), summed=("grad_sets",))
 
     def adjoint_table_sets_dev(self, gX_ptr: int, gU_ptr: int, grad_sets_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.adjoint_table_sets_dev with the same arrays, as adjoint_tables_dev: grad_sets (n_sets,4,n_table) summed over
         the parts in part order (the first part overwrites, every later one adds after the part before it has finished)."""
-        N = self.N
-        for i, (p, (lo, hi)) in enumerate(zip(self.parts, self.bounds)):
-            if i and grad_sets_ptr:
-                self.parts[i - 1].synchronize()
-            p.adjoint_table_sets_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0, grad_sets_ptr,
-                                     slot_grad_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if slot_grad_ptr else 0,
-                                     ok_ptr + 4 * lo if ok_ptr else 0, add=i > 0)
+        self._forward_dev("adjoint_table_sets_dev", _Rows(gX_ptr, "X"), _Rows(gU_ptr, "U"), grad_sets_ptr, _Rows(slot_grad_ptr, "slot"),
+                          _Rows(ok_ptr, "flag"), sum_into=grad_sets_ptr)
 
     # ---- solve records: one record per part (BatchedMPC.record, DESIGN.md §17)
     def record(self, into: SolveRecord | None = None) -> SolveRecord:
@@ -1399,99 +1421,61 @@ class SplitMPC:
 
     def sensitivities(self, trajectory: bool = False):
         """BatchedMPC.sensitivities of every part, stitched in the caller's order."""
-        r = [p.sensitivities(trajectory) for p in self.parts]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        return _stitch([p.sensitivities(trajectory) for p in self.parts])
 
     def sensitivities_dev(self, du0_dp_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.sensitivities_dev of every part into its rows of (B,2,10) doubles / (B,) int32, each on its part's stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.sensitivities_dev(du0_dp_ptr + 8 * NU * 10 * lo if du0_dp_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev("sensitivities_dev", _Rows(du0_dp_ptr, "du0_dp"), _Rows(ok_ptr, "flag"))
 
     def param_sensitivities(self, trajectory: bool = False):
         """BatchedMPC.param_sensitivities of every part, stitched in the caller's order."""
-        r = [p.param_sensitivities(trajectory) for p in self.parts]
-        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+        return _stitch([p.param_sensitivities(trajectory) for p in self.parts], first=("names",))
 
     def param_sensitivities_dev(self, du0_dth_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.param_sensitivities_dev of every part into its rows of (B,2,16) doubles / (B,) int32, each on its part's
         stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.param_sensitivities_dev(du0_dth_ptr + 8 * NU * NTHETA * lo if du0_dth_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev("param_sensitivities_dev", _Rows(du0_dth_ptr, "du0_dtheta"), _Rows(ok_ptr, "flag"))
 
     def adjoint(self, gX=None, gU=None, theta: bool = True):
         """BatchedMPC.adjoint of every part with its rows of the cotangents, stitched in the caller's order."""
-        gX = None if gX is None else np.asarray(gX, dtype=np.float64)
-        gU = None if gU is None else np.asarray(gU, dtype=np.float64)
-        r = [p.adjoint(None if gX is None else gX[lo:hi], None if gU is None else gU[lo:hi], theta)
-             for p, (lo, hi) in zip(self.parts, self.bounds)]
-        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+        r = [p.adjoint(gXp, gUp, theta) for p, gXp, gUp in self._rows_of(_f64(gX), _f64(gU))]
+        return _stitch(r, first=("names",))
 
     def adjoint_dev(self, gX_ptr: int, gU_ptr: int, grad_p_ptr: int = 0, grad_theta_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.adjoint_dev of every part on its rows of (B,N+1,8) / (B,N,2) cotangents into its rows of (B,10) / (B,16)
         doubles / (B,) int32, each on its part's stream."""
-        N = self.N
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.adjoint_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0,
-                          grad_p_ptr + 8 * 10 * lo if grad_p_ptr else 0, grad_theta_ptr + 8 * NTHETA * lo if grad_theta_ptr else 0,
-                          ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev("adjoint_dev", _Rows(gX_ptr, "X"), _Rows(gU_ptr, "U"), _Rows(grad_p_ptr, "p"), _Rows(grad_theta_ptr, "theta"),
+                          _Rows(ok_ptr, "flag"))
 
     def adjoint_tables(self, gX=None, gU=None, slots: bool = False):
         """BatchedMPC.adjoint_tables of every part with its rows of the cotangents: grad_tables summed over the parts in part
         order (on the host), slot_grad and ok stitched in the caller's order."""
-        gX = None if gX is None else np.asarray(gX, dtype=np.float64)
-        gU = None if gU is None else np.asarray(gU, dtype=np.float64)
-        r = [p.adjoint_tables(None if gX is None else gX[lo:hi], None if gU is None else gU[lo:hi], slots)
-             for p, (lo, hi) in zip(self.parts, self.bounds)]
-        out = dict(r[0], ok=np.concatenate([q["ok"] for q in r]))
-        gt = r[0]["grad_tables"].copy()
-        for q in r[1:]:
-            gt += q["grad_tables"]
-        out["grad_tables"] = gt
-        if slots:
-            out["slot_grad"] = np.concatenate([q["slot_grad"] for q in r])
-        return out
+        r = [p.adjoint_tables(gXp, gUp, slots) for p, gXp, gUp in self._rows_of(_f64(gX), _f64(gU))]
+        return _stitch(r, first=("names", "slot_names"), summed=("grad_tables",))
 
     def adjoint_tables_dev(self, gX_ptr: int, gU_ptr: int, grad_tables_ptr: int = 0, slot_grad_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.adjoint_tables_dev with the same arrays: slot_grad (B,N,10) and ok (B,) by rows, each part on its own
         stream, and grad_tables (4,n_table) summed over the parts in part order: the first part overwrites the array, every
         later one adds to it after the part before it has finished (the handle is synchronised in between, so the sum is the
         same from call to call up to each part's own atomic order).  Returns with the parts' work enqueued or done."""
-        N = self.N
-        for i, (p, (lo, hi)) in enumerate(zip(self.parts, self.bounds)):
-            if i and grad_tables_ptr:
-                self.parts[i - 1].synchronize()
-            p.adjoint_tables_dev(gX_ptr + 8 * (N + 1) * NX * lo if gX_ptr else 0, gU_ptr + 8 * N * NU * lo if gU_ptr else 0, grad_tables_ptr,
-                                 slot_grad_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if slot_grad_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0,
-                                 add=i > 0)
+        self._forward_dev("adjoint_tables_dev", _Rows(gX_ptr, "X"), _Rows(gU_ptr, "U"), grad_tables_ptr, _Rows(slot_grad_ptr, "slot"),
+                          _Rows(ok_ptr, "flag"), sum_into=grad_tables_ptr)
 
     def jvp(self, dp=None, dtheta=None):
         """BatchedMPC.jvp of every part with its rows of the directions, stitched in the caller's order."""
-        dp = None if dp is None else np.asarray(dp, dtype=np.float64)
-        dtheta = None if dtheta is None else np.asarray(dtheta, dtype=np.float64)
-        r = [p.jvp(None if dp is None else dp[lo:hi], None if dtheta is None else dtheta[lo:hi]) for p, (lo, hi) in zip(self.parts, self.bounds)]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        return _stitch([p.jvp(dpp, dthp) for p, dpp, dthp in self._rows_of(_f64(dp), _f64(dtheta))])
 
     def jvp_dev(self, dp_ptr: int, dtheta_ptr: int, tX_ptr: int = 0, tU_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.jvp_dev of every part on its rows of (B,10) / (B,16) directions into its rows of (B,N+1,8) / (B,N,2)
         doubles / (B,) int32, each on its part's stream."""
-        N = self.N
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.jvp_dev(dp_ptr + 8 * 10 * lo if dp_ptr else 0, dtheta_ptr + 8 * NTHETA * lo if dtheta_ptr else 0,
-                      tX_ptr + 8 * (N + 1) * NX * lo if tX_ptr else 0, tU_ptr + 8 * N * NU * lo if tU_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev("jvp_dev", _Rows(dp_ptr, "p"), _Rows(dtheta_ptr, "theta"), _Rows(tX_ptr, "X"), _Rows(tU_ptr, "U"), _Rows(ok_ptr, "flag"))
 
     def _jvp_tables_parts(self, name, dp, dtables, dslot):
-        dp = None if dp is None else np.asarray(dp, dtype=np.float64)
-        dslot = None if dslot is None else np.asarray(dslot, dtype=np.float64)
-        r = [getattr(p, name)(None if dp is None else dp[lo:hi], dtables, None if dslot is None else dslot[lo:hi])
-             for p, (lo, hi) in zip(self.parts, self.bounds)]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        return _stitch([getattr(p, name)(dpp, dtables, dslotp) for p, dpp, dslotp in self._rows_of(_f64(dp), _f64(dslot))])
 
     def _jvp_tables_parts_dev(self, name, dp_ptr, dtables_ptr, dslot_ptr, tX_ptr, tU_ptr, ok_ptr):
-        N = self.N
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            getattr(p, name)(dp_ptr + 8 * 10 * lo if dp_ptr else 0, dtables_ptr, dslot_ptr + 8 * N * len(TABLE_SLOT_NAMES) * lo if dslot_ptr else 0,
-                             tX_ptr + 8 * (N + 1) * NX * lo if tX_ptr else 0, tU_ptr + 8 * N * NU * lo if tU_ptr else 0,
-                             ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev(name, _Rows(dp_ptr, "p"), dtables_ptr, _Rows(dslot_ptr, "slot"), _Rows(tX_ptr, "X"), _Rows(tU_ptr, "U"),
+                          _Rows(ok_ptr, "flag"))
 
     def jvp_tables(self, dp=None, dtables=None, dslot=None):
         """BatchedMPC.jvp_tables of every part: dtables to every part, dp and dslot by the part's rows, the results stitched in
@@ -1518,27 +1502,23 @@ class SplitMPC:
             raise ValueError(f"set_u_prev: expected {self.B} inputs of dimension {NU}, got array of shape {u.shape}")
         if not np.isfinite(u).all():  # (the whole batch checked first: a bad row changes no part)
             raise ValueError(f"set_u_prev: non-finite u_prev of instance {int(np.argwhere(~np.isfinite(u))[0][0])}")
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.set_u_prev(u[lo:hi])
+        for p, mine in self._rows_of(u):
+            p.set_u_prev(mine)
 
     def set_u_prev_dev(self, u_prev_ptr: int):
         """BatchedMPC.set_u_prev_dev of every part on its rows of (B,2) doubles, each on its part's stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.set_u_prev_dev(u_prev_ptr + 8 * NU * lo)
+        self._forward_dev("set_u_prev_dev", _Rows(u_prev_ptr, "u"))
 
     def plant_sensitivities(self, x, u, n_sub: int = 400, theta: bool = True):
         """BatchedMPC.plant_sensitivities of every part on its rows, stitched in the caller's order."""
-        x, u = np.asarray(x, dtype=np.float64).reshape(self.B, NX), np.asarray(u, dtype=np.float64).reshape(self.B, NU)
-        r = [p.plant_sensitivities(x[lo:hi], u[lo:hi], n_sub, theta) for p, (lo, hi) in zip(self.parts, self.bounds)]
-        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+        x, u = np.asarray(x, dtype=np.float64).reshape(self._shape("x")), np.asarray(u, dtype=np.float64).reshape(self._shape("u"))
+        return _stitch([p.plant_sensitivities(xp, up, n_sub, theta) for p, xp, up in self._rows_of(x, u)], first=("names",))
 
     def plant_sensitivities_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int = 0, dx_ptr: int = 0, du_ptr: int = 0, dtheta_ptr: int = 0,
                                 n_sub: int = 400):
         """BatchedMPC.plant_sensitivities_dev of every part on its rows, each on its part's stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.plant_sensitivities_dev(x_ptr + 8 * NX * lo, u_ptr + 8 * NU * lo, xn_ptr + 8 * NX * lo if xn_ptr else 0,
-                                      dx_ptr + 8 * NX * NX * lo if dx_ptr else 0, du_ptr + 8 * NX * NU * lo if du_ptr else 0,
-                                      dtheta_ptr + 8 * NX * NTHETA * lo if dtheta_ptr else 0, n_sub)
+        self._forward_dev("plant_sensitivities_dev", _Rows(x_ptr, "x"), _Rows(u_ptr, "u"), _Rows(xn_ptr, "x"), _Rows(dx_ptr, "plant_dx"),
+                          _Rows(du_ptr, "plant_du"), _Rows(dtheta_ptr, "plant_dtheta"), n_sub)
 
     def loop_begin(self, mode: int = 3):
         for p in self.parts:
@@ -1546,23 +1526,19 @@ class SplitMPC:
 
     def loop_tick_dev(self, x_ptr: int, u_ptr: int, xn_ptr: int, n_sub: int = 400):
         """BatchedMPC.loop_tick_dev of every part on its rows of x (B,8), u (B,2), xn (B,8), each on its part's stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.loop_tick_dev(x_ptr + 8 * NX * lo, u_ptr + 8 * NU * lo, xn_ptr + 8 * NX * lo, n_sub)
+        self._forward_dev("loop_tick_dev", _Rows(x_ptr, "x"), _Rows(u_ptr, "u"), _Rows(xn_ptr, "x"), n_sub)
 
     def loop_tick(self, x, u0, n_sub: int = 400):
-        x, u0 = np.asarray(x, dtype=np.float64).reshape(self.B, NX), np.asarray(u0, dtype=np.float64).reshape(self.B, NU)
-        return np.concatenate([p.loop_tick(x[lo:hi], u0[lo:hi], n_sub) for p, (lo, hi) in zip(self.parts, self.bounds)])
+        x, u0 = np.asarray(x, dtype=np.float64).reshape(self._shape("x")), np.asarray(u0, dtype=np.float64).reshape(self._shape("u"))
+        return np.concatenate([p.loop_tick(xp, up, n_sub) for p, xp, up in self._rows_of(x, u0)])
 
     def loop_sensitivities(self):
         """BatchedMPC.loop_sensitivities of every part, stitched in the caller's order."""
-        r = [p.loop_sensitivities() for p in self.parts]
-        return {k: (r[0][k] if k == "names" else np.concatenate([q[k] for q in r])) for k in r[0]}
+        return _stitch([p.loop_sensitivities() for p in self.parts], first=("names",))
 
     def loop_sensitivities_dev(self, dx_ptr: int = 0, du_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.loop_sensitivities_dev of every part into its rows of (B,8,24) / (B,2,24) doubles / (B,) int32."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.loop_sensitivities_dev(dx_ptr + 8 * NX * NLOOP * lo if dx_ptr else 0, du_ptr + 8 * NU * NLOOP * lo if du_ptr else 0,
-                                     ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev("loop_sensitivities_dev", _Rows(dx_ptr, "loop_dx"), _Rows(du_ptr, "loop_du"), _Rows(ok_ptr, "flag"))
 
     def loop_end(self):
         for p in self.parts:
@@ -1570,53 +1546,44 @@ class SplitMPC:
 
     def prediction_dev(self, X_ptr: int = 0, U_ptr: int = 0):
         """BatchedMPC.prediction_dev of every part into its rows of (B,N+1,8) / (B,N,2) doubles, each on its part's stream."""
-        N = self.N
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.prediction_dev(X_ptr + 8 * (N + 1) * NX * lo if X_ptr else 0, U_ptr + 8 * N * NU * lo if U_ptr else 0)
+        self._forward_dev("prediction_dev", _Rows(X_ptr, "X"), _Rows(U_ptr, "U"))
 
     # ---- the feedback policy (BatchedMPC.policy, DESIGN.md §18): by global index, each part fills its rows
     def policy(self):
         """BatchedMPC.policy of every part, stitched in the caller's order."""
-        r = [p.policy() for p in self.parts]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        return _stitch([p.policy() for p in self.parts])
 
     def policy_dev(self, K_ptr: int = 0, Kv_ptr: int = 0, ok_ptr: int = 0):
         """BatchedMPC.policy_dev of every part into its rows of (B,N,2,8) / (B,N,2,2) doubles / (B,) int32, each on its part's stream."""
-        N = self.N
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.policy_dev(K_ptr + 8 * N * NU * NX * lo if K_ptr else 0, Kv_ptr + 8 * N * NU * NU * lo if Kv_ptr else 0, ok_ptr + 4 * lo if ok_ptr else 0)
+        self._forward_dev("policy_dev", _Rows(K_ptr, "K"), _Rows(Kv_ptr, "Kv"), _Rows(ok_ptr, "flag"))
 
     def policy_step(self, k: int, x, v=None, clip: bool = False):
         """BatchedMPC.policy_step with the rows split across the parts (shapes and finiteness checked first: a bad row reaches no part)."""
-        x = _shaped("policy_step", "x", x, (self.B, NX))
-        v = None if v is None else _shaped("policy_step", "v", v, (self.B, NU))
+        x = _shaped("policy_step", "x", x, self._shape("x"))
+        v = _shaped_or_none("policy_step", "v", v, self._shape("u"))
         if not (np.isfinite(x).all() and (v is None or np.isfinite(v).all())):
             raise ValueError("policy_step: non-finite x or v")
-        return np.concatenate([p.policy_step(k, x[lo:hi], None if v is None else v[lo:hi], clip) for p, (lo, hi) in zip(self.parts, self.bounds)])
+        return np.concatenate([p.policy_step(k, xp, vp, clip) for p, xp, vp in self._rows_of(x, v)])
 
     def policy_step_dev(self, k: int, x_ptr: int, v_ptr: int, u_ptr: int, clip: bool = False):
         """BatchedMPC.policy_step_dev of every part on its rows of x (B,8), v (B,2; 0: V_k), u (B,2), each on its part's stream."""
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.policy_step_dev(k, x_ptr + 8 * NX * lo, v_ptr + 8 * NU * lo if v_ptr else 0, u_ptr + 8 * NU * lo, clip)
+        self._forward_dev("policy_step_dev", k, _Rows(x_ptr, "x"), _Rows(v_ptr, "u"), _Rows(u_ptr, "u"), clip)
 
     def policy_run_dev(self, k0: int, n: int, x_ptr: int, v_ptr: int = 0, n_sub: int = 400, clip: bool = False, u_log_ptr: int = 0,
                        x_log_ptr: int = 0):
         """BatchedMPC.policy_run_dev of every part on its rows of x (B,8), v (B,2), u_log (B,n,2), x_log (B,n,8), each on its
         part's stream."""
         n = int(n)
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.policy_run_dev(k0, n, x_ptr + 8 * NX * lo, v_ptr + 8 * NU * lo if v_ptr else 0, n_sub, clip,
-                             u_log_ptr + 8 * NU * n * lo if u_log_ptr else 0, x_log_ptr + 8 * NX * n * lo if x_log_ptr else 0)
+        self._forward_dev("policy_run_dev", k0, n, _Rows(x_ptr, "x"), _Rows(v_ptr, "u"), n_sub, clip, _Rows(u_log_ptr, "u_log", n),
+                          _Rows(x_log_ptr, "x_log", n))
 
     def policy_last_dev(self, n: int, u_log_ptr: int, u_ptr: int):
         """BatchedMPC.policy_last_dev of every part on its rows of u_log (B,n,2) and u (B,2), each on its part's stream."""
         n = int(n)
-        for p, (lo, hi) in zip(self.parts, self.bounds):
-            p.policy_last_dev(n, u_log_ptr + 8 * NU * n * lo, u_ptr + 8 * NU * lo)
+        self._forward_dev("policy_last_dev", n, _Rows(u_log_ptr, "u_log", n), _Rows(u_ptr, "u"))
 
     def policy_run(self, k0: int, n: int, x, v=None, n_sub: int = 400, clip: bool = False):
         """BatchedMPC.policy_run with the rows split across the parts, stitched in the caller's order."""
-        x = _shaped("policy_run", "x", x, (self.B, NX))
-        v = None if v is None else _shaped("policy_run", "v", v, (self.B, NU))
-        r = [p.policy_run(k0, n, x[lo:hi], None if v is None else v[lo:hi], n_sub, clip) for p, (lo, hi) in zip(self.parts, self.bounds)]
-        return {k: np.concatenate([q[k] for q in r]) for k in r[0]}
+        x = _shaped("policy_run", "x", x, self._shape("x"))
+        v = _shaped_or_none("policy_run", "v", v, self._shape("u"))
+        return _stitch([p.policy_run(k0, n, xp, vp, n_sub, clip) for p, xp, vp in self._rows_of(x, v)])
