@@ -5,6 +5,83 @@
 
 namespace ltompc {
 
+// ------------------------------------------------------------------------------------------ where the line search reads
+// The operands of d_linesearch that belong to the instance's iterate and step (not to the candidate): the planes themselves
+// (SrcPlanes: k_linesearch, every wide kernel) or the copy that k_step1 keeps in LDS (StepStage, below).  One text, two sources:
+// every accessor of SrcPlanes is the expression d_linesearch had in its place.
+struct SrcPlanes {
+  static constexpr bool staged = false;
+  __device__ __forceinline__ double eps(const Work& W, const int b) const { return W.st[(size_t)ST_EPS * W.Bp + b]; }
+  __device__ __forceinline__ double rho(const Work& W, const int b) const { return W.st[(size_t)ST_RHO * W.Bp + b]; }
+  __device__ __forceinline__ double apri(const Work& W, const int b, const int N, const int kk) const { return PL(W.SP, SP_apri, kk, N); }
+  __device__ __forceinline__ double Xn(const Work& W, const int b, const int N, const int i, const int k) const {  // node k, node 0 the measured state
+    return k == 0 ? W.x0[(size_t)i * W.Bp + b] : PL(W.X, i, k, N + 1);
+  }
+  __device__ __forceinline__ double X(const Work& W, const int b, const int N, const int i, const int k) const { return PL(W.X, i, k, N + 1); }
+  __device__ __forceinline__ double dX(const Work& W, const int b, const int N, const int i, const int k) const { return PL(W.dX, i, k, N + 1); }
+  __device__ __forceinline__ double C(const Work& W, const int b, const int N, const int i, const int k) const { return PL(W.C, i, k, N); }
+  __device__ __forceinline__ double dC(const Work& W, const int b, const int N, const int i, const int k) const { return PL(W.dC, i, k, N); }
+  __device__ __forceinline__ double U(const Work& W, const int b, const int N, const int i, const int k) const { return PL(W.U, i, k, N); }
+  __device__ __forceinline__ double dU(const Work& W, const int b, const int N, const int i, const int k) const { return PL(W.dU, i, k, N); }
+  __device__ __forceinline__ double Up(const Work& W, const int b, const int N, const int i, const int k) const {  // slot k - 1, slot -1 the applied input
+    return k ? PL(W.U, i, k - 1, N) : W.uprev[(size_t)i * W.Bp + b];
+  }
+  __device__ __forceinline__ double dUp(const Work& W, const int b, const int N, const int i, const int k) const { return k ? PL(W.dU, i, k - 1, N) : 0.0; }
+  __device__ __forceinline__ double T(const Work& W, const int b, const int N, const int m, const int k) const { return PL(W.T, m, k, N); }
+  __device__ __forceinline__ double dT(const Work& W, const int b, const int N, const int m, const int k) const { return PL(W.dT, m, k, N); }
+};
+
+// k_step1's copy of one instance's operands in LDS.  The planes are [field][k][Bp], instance fastest, and a workgroup of k_step1
+// holds ONE instance: every word it loads is a 64-byte sector of its own, and all of them pass the CU's one cache port.  The
+// eight candidates of a slot, the neighbour slots (x_k is x_{k+1} of the slot before, u_{k-1} its u_k) and the update after the
+// pick asked for each word about seven times; staged, each word passes the port once (d_step1_stage) and the rest are LDS reads.
+// Layout, in doubles: eps, rho | the N partials SP_apri | `cols` columns of `stride` words, column = node or slot minus k0, the
+// word of a column = the row: x_i, dx_i at 2 i, 2 i + 1 (column = node, node 0 of X is W.x0), c_i, dc_i at SG_C + 2 i, + 1 (column =
+// slot), u_i, du_i at SG_U + 2 i, + 1 (column = slot + 1, so that column 0 of the first window is slot -1: W.uprev and a step of 0),
+// t_m, dt_m at SG_T + 2 m, + 1 for the R = ni + NNL + nel rows of T (the slacks and the elastic variables, every row the planes
+// have; column = slot).  A lane reads through ONE address, its column's, with the row as the instruction's constant offset, a
+// word and its step side by side in one read; stride is odd, so lanes with consecutive k read without a bank conflict, and the
+// candidates of one slot read the same word (a broadcast).  (Rows of `cols` words each, [field][k], need an address per row:
+// 119 SGPRs spilled and 10 VGPRs with them, where this layout spills 80 and none.)
+// A window holds the slots k0 .. k0 + ks - 1, ks = cols - 1 (their nodes k0 .. k0 + ks need cols columns), as many as the
+// array has room for beside the N partials: at the reference's bound pattern (R = 26) N <= 67 is ONE window and the update reads it
+// too (`whole`); a longer horizon or a larger pattern takes several windows, one after the other, and its update reads the planes.
+constexpr int STG_WORDS = 6144;  // 48 KiB, static: three workgroups a CU, as many as the registers allow
+enum : int { SG_X = 0, SG_C = 16, SG_U = 32, SG_T = 36 };
+struct StepStage {
+  static constexpr bool staged = true;
+  double* s;       // the workgroup's array
+  int N, R;        // horizon; rows of T (and of dT)
+  int stride, ks;  // words of a column; slots of a window
+  int k0;          // first slot of the window held
+  __device__ __forceinline__ bool whole() const { return N <= ks; }  // the one window is the instance
+  __device__ __forceinline__ const double* at(const int row, const int col) const { return s + 2 + N + (col - k0) * stride + row; }
+  __device__ __forceinline__ double eps(const Work&, const int) const { return s[0]; }
+  __device__ __forceinline__ double rho(const Work&, const int) const { return s[1]; }
+  __device__ __forceinline__ double apri(const Work&, const int, const int, const int kk) const { return s[2 + kk]; }
+  __device__ __forceinline__ double Xn(const Work&, const int, const int, const int i, const int k) const { return *at(SG_X + 2 * i, k); }
+  __device__ __forceinline__ double X(const Work&, const int, const int, const int i, const int k) const { return *at(SG_X + 2 * i, k); }
+  __device__ __forceinline__ double dX(const Work&, const int, const int, const int i, const int k) const { return *at(SG_X + 2 * i + 1, k); }
+  __device__ __forceinline__ double C(const Work&, const int, const int, const int i, const int k) const { return *at(SG_C + 2 * i, k); }
+  __device__ __forceinline__ double dC(const Work&, const int, const int, const int i, const int k) const { return *at(SG_C + 2 * i + 1, k); }
+  __device__ __forceinline__ double U(const Work&, const int, const int, const int i, const int k) const { return *at(SG_U + 2 * i, k + 1); }
+  __device__ __forceinline__ double dU(const Work&, const int, const int, const int i, const int k) const { return *at(SG_U + 2 * i + 1, k + 1); }
+  __device__ __forceinline__ double Up(const Work&, const int, const int, const int i, const int k) const { return *at(SG_U + 2 * i, k); }
+  __device__ __forceinline__ double dUp(const Work&, const int, const int, const int i, const int k) const { return *at(SG_U + 2 * i + 1, k); }
+  __device__ __forceinline__ double T(const Work&, const int, const int, const int m, const int k) const { return *at(SG_T + 2 * m, k); }
+  __device__ __forceinline__ double dT(const Work&, const int, const int, const int m, const int k) const { return *at(SG_T + 2 * m + 1, k); }
+};
+// words of a column for R rows of T (odd), and the columns for horizon N: what is left beside eps, rho and the partials, over the
+// stride; at most 128 columns, so that the 320 lanes are at least two rows of columns (d_step1_stage).
+// (tests/test_host_harness_step1_stage.py derives the last horizon of one window from the same lines.)
+__host__ __device__ constexpr int stage_stride(const int R) { return SG_T + 2 * R + 1; }
+__host__ __device__ constexpr int stage_cols(const int N, const int R) {
+  const int c = (STG_WORDS - 2 - N) / stage_stride(R);
+  return c < 128 ? c : 128;
+}
+static_assert(stage_cols(4096, MAX_NI + NNL + NEL) >= 2, "a window holds at least one slot at the longest horizon and the largest pattern");
+static_assert(stage_cols(40, 23 + NNL + NEL) > 40, "the benchmark's instance (N = 40, the reference's pattern, with or without the ellipse) is one window");
+
 // ------------------------------------------------------------------------------------------ k_linesearch
 // candidate 0 is the current point (alpha = 0); candidate l >= 1 has alpha = a_pri * 2^-(l-1).
 // LS plane layout: [3 * (n_ls + 1)][N][Bp] : theta, cost, sum log t per candidate.
@@ -12,34 +89,36 @@ namespace ltompc {
 // for every instance; phase 1 evaluates the remaining candidates for the instances whose first candidate was rejected.
 // Filter measures (theta, cost, sum log t) of the step candidates l_begin..l_end of interval k of instance b;
 // candidate l >= 1 has alpha = a_pri * 2^-(l-1) (l = 0, the current point, is written by k_eval).
-template <class BP, bool PIN, bool ELL, bool PI = false, bool TS = false>
+template <class BP, bool PIN, bool ELL, bool PI = false, bool TS = false, class SRC = SrcPlanes>
 __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, const int k, const int b, const int l_begin,
-                                             const int l_end) {
+                                             const int l_end, const SRC& src = SRC()) {
   const int N = W.N;
   const double hdt = K.o.t_step;
-  if (W.si[(size_t)SI_DONE * W.Bp + b] || !W.si[(size_t)SI_STEP * W.Bp + b]) return;  // no step this launch
-  const double eps = W.st[(size_t)ST_EPS * W.Bp + b], rho = W.st[(size_t)ST_RHO * W.Bp + b];
+  if constexpr (!SRC::staged) {  // (k_step1 has tested the two flags for the workgroup before it staged anything)
+    if (W.si[(size_t)SI_DONE * W.Bp + b] || !W.si[(size_t)SI_STEP * W.Bp + b]) return;  // no step this launch
+  }
+  const double eps = src.eps(W, b), rho = src.rho(W, b);
   double a_pri = 1.0;
   for (int kk = 0; kk < N; kk += 20) {  // twenty loads in flight per round trip (a plain loop waits for every single one)
     double v20[20];
 #pragma unroll
-    for (int q = 0; q < 20; q++) v20[q] = PL(W.SP, SP_apri, kk + q < N ? kk + q : N - 1, N);
+    for (int q = 0; q < 20; q++) v20[q] = src.apri(W, b, N, kk + q < N ? kk + q : N - 1);
 #pragma unroll
     for (int q = 0; q < 20; q++) a_pri = fmin(a_pri, v20[q]);
   }
   double xk[8], xp[8], c[8], u[2], v[2], dxk[8], dxp[8], dc[8], du[2], dv[2];
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    xk[i] = k == 0 ? W.x0[(size_t)i * W.Bp + b] : PL(W.X, i, k, N + 1);
-    dxk[i] = PL(W.dX, i, k, N + 1);
-    xp[i] = PL(W.X, i, k + 1, N + 1), dxp[i] = PL(W.dX, i, k + 1, N + 1);
-    c[i] = PL(W.C, i, k, N), dc[i] = PL(W.dC, i, k, N);
+    xk[i] = src.Xn(W, b, N, i, k);
+    dxk[i] = src.dX(W, b, N, i, k);
+    xp[i] = src.X(W, b, N, i, k + 1), dxp[i] = src.dX(W, b, N, i, k + 1);
+    c[i] = src.C(W, b, N, i, k), dc[i] = src.dC(W, b, N, i, k);
   }
 #pragma unroll
   for (int i = 0; i < 2; i++) {
-    u[i] = PL(W.U, i, k, N), du[i] = PL(W.dU, i, k, N);
-    v[i] = k ? PL(W.U, i, k - 1, N) : W.uprev[(size_t)i * W.Bp + b];
-    dv[i] = k ? PL(W.dU, i, k - 1, N) : 0.0;
+    u[i] = src.U(W, b, N, i, k), du[i] = src.dU(W, b, N, i, k);
+    v[i] = src.Up(W, b, N, i, k);
+    dv[i] = src.dUp(W, b, N, i, k);
   }
   const bool nl = (k + 1 <= N - 1);
   // candidate index l: 0 = current point, l >= 1: alpha = a_pri * 2^-(l-1)
@@ -73,15 +152,15 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
     const auto fetch_track = [&](const int m0) {  // (these planes exist for every slot: k_expand writes zeros in the last one)
 #pragma unroll
       for (int q = 0; q < NTR; q++) {
-        tn[q] = PL(W.T, m0 + q, k, N), dtn[q] = PL(W.dT, m0 + q, k, N);
-        en[q] = PL(W.T, K.bd.ni + q, k, N), den[q] = PL(W.dT, K.bd.ni + q, k, N);
+        tn[q] = src.T(W, b, N, m0 + q, k), dtn[q] = src.dT(W, b, N, m0 + q, k);
+        en[q] = src.T(W, b, N, K.bd.ni + q, k), den[q] = src.dT(W, b, N, K.bd.ni + q, k);
       }
     };
     // compile-time bound pattern: the slacks of the simple bounds in one batch of loads as well.  PIN: in the batch of the knots
     // (k_linesearch); else on their own after the cost (k_step1, two wavefronts per SIMD: 80 registers more in the batch of the
     // knots and it spills)
     double t0[BP::fixed ? MAX_NI : 1] = {}, d0[BP::fixed ? MAX_NI : 1] = {};  // (zero: the pinning below touches whole chunks of 8)
-    const auto fetch_bounds = [&] { for_each_bound<BP>(K.p, [&](int mm, int, int, double, double) { t0[mm] = PL(W.T, mm, k, N), d0[mm] = PL(W.dT, mm, k, N); }); };
+    const auto fetch_bounds = [&] { for_each_bound<BP>(K.p, [&](int mm, int, int, double, double) { t0[mm] = src.T(W, b, N, mm, k), d0[mm] = src.dT(W, b, N, mm, k); }); };
     const int nb = BP::fixed ? for_each_bound<BP>(K.p, [](int, int, int, double, double) {}) : 0;
     if (BP::fixed && PIN) fetch_bounds();
     if (BP::fixed) fetch_track(nb);
@@ -127,7 +206,9 @@ __device__ __forceinline__ void d_linesearch(const Consts& K, const Work& W, con
     }
     const int m = for_each_bound<BP>(K.p, [&](int mm, int kind, int jj, double sg, double val) {
       const double xv = kind == 0 ? tu[jj] : (kind == 1 ? tc[jj] : txp[jj]);
-      const double t = BP::fixed ? tt[mm] : PL(W.T, mm, k, N) + alpha * PL(W.dT, mm, k, N);
+      double t;  // (the planes' form names no `src`: captured here, it changed the instructions of k_linesearch<BoundsAny>)
+      if constexpr (SRC::staged) t = BP::fixed ? tt[mm] : src.T(W, b, N, mm, k) + alpha * src.dT(W, b, N, mm, k);
+      else t = BP::fixed ? tt[mm] : PL(W.T, mm, k, N) + alpha * PL(W.dT, mm, k, N);
       th += fabs(sg * (xv - val) + t), pr *= t;
       if ((mm & 7) == 7) sl += log(pr), pr = 1.0;
     });
@@ -643,8 +724,34 @@ __device__ __forceinline__ void upd_store_quads(const Consts& K, const Work& W, 
     }
 }
 
+// ... and with the line search's operands staged (StepStage::whole): of a row's 24 words the planes give the 10 that the line
+// search does not read - the multiplier pairs and (nu_m, dn_m) - and the window the other 14, through the same clamped indices.
+__device__ __forceinline__ void upd_load_mults(const Consts& K, const Work& W, const int k, const int r, const int b, UpdRow& v) {
+  const int N = W.N, ni = K.bd.ni, nel = K.bd.nel, nact = (k + 1 <= N - 1) ? ni : ni - 3 - nel;
+  const int last = nact > 0 ? nact - 1 : 0;
+  v.a[2] = PL(W.L1, r, k, N), v.d[2] = PL(W.nL1, r, k, N), v.a[3] = PL(W.L2, r, k, N), v.d[3] = PL(W.nL2, r, k, N);
+#pragma unroll
+  for (int q = 0; q < UPD_QUADS; q++) {
+    const int m = r + 8 * q < nact ? r + 8 * q : last;
+    v.nu[q] = PL(W.NU, m, k, N), v.dn[q] = PL(W.dNU, m, k, N);
+  }
+}
+__device__ __forceinline__ void upd_take_staged(const Consts& K, const Work& W, const StepStage& S, const int k, const int r, const int b, UpdRow& v) {
+  const int N = W.N, ni = K.bd.ni, nel = K.bd.nel, nact = (k + 1 <= N - 1) ? ni : ni - 3 - nel;
+  const int last = nact > 0 ? nact - 1 : 0;
+  const int ru = r < 2 ? r : 1, re = ni + (r < 3 + nel ? r : 0);
+  v.a[0] = S.X(W, b, N, r, k + 1), v.d[0] = S.dX(W, b, N, r, k + 1), v.a[1] = S.C(W, b, N, r, k), v.d[1] = S.dC(W, b, N, r, k);
+  v.a[4] = S.U(W, b, N, ru, k), v.d[4] = S.dU(W, b, N, ru, k);
+  v.e = S.T(W, b, N, re, k), v.de = S.dT(W, b, N, re, k);
+#pragma unroll
+  for (int q = 0; q < UPD_QUADS; q++) {
+    const int m = r + 8 * q < nact ? r + 8 * q : last;
+    v.t[q] = S.T(W, b, N, m, k), v.dt[q] = S.dT(W, b, N, m, k);
+  }
+}
+
 // wavefronts 1..4, beside d_pick: the operands of the first UPD_ROUNDS * 32 slots, one batch
-__device__ __forceinline__ void d_update_fetch(const Consts& K, const Work& W, const int tid, const int b, UpdRegs& R) {
+__device__ __forceinline__ void d_update_fetch(const Consts& K, const Work& W, const StepStage& S, const int tid, const int b, UpdRegs& R) {
   const int N = W.N, w = tid - 64;
 #pragma unroll
   for (int j = 0; j < UPD_ROUNDS; j++) {
@@ -652,7 +759,10 @@ __device__ __forceinline__ void d_update_fetch(const Consts& K, const Work& W, c
     //  and their 4600 repeated loads made the fetch longer than the pick it runs beside - the workgroup's loads go through one
     //  cache port, a 64-byte sector per lane and load)
     const int k = 32 * j + (w >> 3);
-    if (k < N) upd_load_pairs(K, W, k, w & 7, b, R.row[j]), upd_load_quads(K, W, k, w & 7, b, 0, R.row[j]);
+    if (k < N) {
+      if (S.whole()) upd_load_mults(K, W, k, w & 7, b, R.row[j]);
+      else upd_load_pairs(K, W, k, w & 7, b, R.row[j]), upd_load_quads(K, W, k, w & 7, b, 0, R.row[j]);
+    }
   }
 #if defined(__HIP_DEVICE_COMPILE__)
   // in registers HERE, while the pick runs: not sunk to the stores behind the barrier
@@ -668,7 +778,10 @@ __device__ __forceinline__ void d_update_fetch(const Consts& K, const Work& W, c
 }
 
 // all wavefronts, after the pick: the state it left, one round trip, then the stores
-__device__ __forceinline__ void d_update_store(const Consts& K, const Work& W, const int tid, const int b, const UpdRegs& R) {
+// (whole: the words of X, dX, C, dC, U, dU, T, dT come from the window.  Nothing has written them in the planes since they were
+//  staged: d_linesearch stores to W.LS only and d_pick to W.st, W.si, W.filt and ls_list only, and the stores below are this
+//  kernel's first to the iterate.)
+__device__ __forceinline__ void d_update_store(const Consts& K, const Work& W, const StepStage& S, const int tid, const int b, UpdRegs& R) {
   const int N = W.N;
   int shift = W.si[(size_t)SI_SHIFT * W.Bp + b], done = W.si[(size_t)SI_DONE * W.Bp + b], step = W.si[(size_t)SI_STEP * W.Bp + b];
   double alpha = W.st[(size_t)ST_ALPHA * W.Bp + b], a_dua = W.st[(size_t)ST_ADUA * W.Bp + b];
@@ -691,7 +804,10 @@ __device__ __forceinline__ void d_update_store(const Consts& K, const Work& W, c
 #pragma unroll
   for (int j = 0; j < UPD_ROUNDS; j++) {
     const int k = 32 * j + (w >> 3);
-    if (k < N) upd_store_pairs(K, W, k, r, b, alpha, rho, R.row[j]), upd_store_quads(K, W, k, r, b, 0, alpha, a_dua, mu, R.row[j]);
+    if (k < N) {
+      if (S.whole()) upd_take_staged(K, W, S, k, r, b, R.row[j]);
+      upd_store_pairs(K, W, k, r, b, alpha, rho, R.row[j]), upd_store_quads(K, W, k, r, b, 0, alpha, a_dua, mu, R.row[j]);
+    }
   }
   // what was not held: slots from UPD_ROUNDS * 32 on, inequalities from UPD_QUADS * 8 on - load a batch, then store it
   const int ni = K.bd.ni;
@@ -709,6 +825,85 @@ __device__ __forceinline__ void d_update_store(const Consts& K, const Work& W, c
   }
 }
 
+
+// ------------------------------------------------------------------------------------------ k_step1's staging
+// The view of the workgroup's array for this handle's horizon and bound pattern (block-uniform).
+__device__ __forceinline__ StepStage step_stage(const Consts& K, const Work& W, double* s) {
+  StepStage S;
+  S.s = s, S.N = W.N, S.R = K.bd.ni + NNL + K.bd.nel;
+  S.stride = stage_stride(S.R), S.ks = stage_cols(S.N, S.R) - 1, S.k0 = 0;
+  return S;
+}
+// All 320 lanes: the window of the slots k0 .. k0 + cnt - 1 into LDS, each word loaded once.  Lane tid owns column
+// col = tid % (cnt + 1) of the rows tid / (cnt + 1) + j * rpp of every array, rpp = 320 / (cnt + 1) rows of lanes (at N = 40: 7, 287
+// lanes at work; stage_cols keeps rpp >= 2, so an array of 8 rows is at most 4 passes).  Per array and pass the row is the same
+// expression in every lane - no pointer is selected per lane - and a lane without a word (past the array's last row, in the last
+// column of an array of slots, in the partial last row of lanes) loads nothing: a pass without lanes is a branch taken.  The loads
+// of X, dX, C, dC, U, dU, of the first STG_TQ passes of T and dT, of eps, rho and the partials are ONE batch, in registers before
+// the first write; further passes of T and dT (more than STG_TQ * rpp rows: at N = 40 none) follow batch by batch.  eps, rho and
+// the N partials SP_apri go with the first window and stay for the later ones.  The caller's barriers stand between this and the
+// readers, and between the readers and the next window.
+constexpr int STG_TQ = 4;
+__device__ __forceinline__ void d_step1_stage(const Work& W, const StepStage& S, const int tid, const int b, const int cnt) {
+  const int N = S.N, R = S.R, c1 = cnt + 1, rpp = 320 / c1;
+  const int row0 = tid / c1, col = tid - row0 * c1, kn = S.k0 + col;
+  const bool lane = row0 < rpp, slotc = lane && col < cnt, first = S.k0 == 0;
+  double* const dst = S.s + 2 + N + col * S.stride;
+  double x[4] = {}, dx[4] = {}, c[4] = {}, dc[4] = {}, u = 0.0, du = 0.0, t[STG_TQ] = {}, dt[STG_TQ] = {}, ap = 0.0, er = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = row0 + j * rpp;
+    if (lane && r < 8) {  // column = node; node 0 of X is the measured state
+      if (kn == 0) x[j] = W.x0[(size_t)r * W.Bp + b];
+      else x[j] = PL(W.X, r, kn, N + 1);
+      dx[j] = PL(W.dX, r, kn, N + 1);
+    }
+    if (slotc && r < 8) c[j] = PL(W.C, r, kn, N), dc[j] = PL(W.dC, r, kn, N);
+  }
+  if (lane && row0 < 2) {  // column = slot + 1; slot -1 of U is the applied input, its step 0
+    if (kn == 0) u = W.uprev[(size_t)row0 * W.Bp + b];
+    else u = PL(W.U, row0, kn - 1, N), du = PL(W.dU, row0, kn - 1, N);
+  }
+  const auto load_t = [&](const int rb) {
+#pragma unroll
+    for (int j = 0; j < STG_TQ; j++) {
+      const int r = rb + row0 + j * rpp;
+      if (slotc && r < R) t[j] = PL(W.T, r, kn, N), dt[j] = PL(W.dT, r, kn, N);
+    }
+  };
+  load_t(0);
+  if (first && tid < N) ap = PL(W.SP, SP_apri, tid, N);
+  if (first && tid >= 318) er = W.st[(size_t)(tid == 318 ? ST_EPS : ST_RHO) * W.Bp + b];
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(dx[0]), "+v"(dx[1]), "+v"(dx[2]), "+v"(dx[3]), "+v"(c[0]), "+v"(c[1]),
+                    "+v"(c[2]), "+v"(c[3]), "+v"(dc[0]), "+v"(dc[1]), "+v"(dc[2]), "+v"(dc[3]), "+v"(u), "+v"(du), "+v"(t[0]), "+v"(t[1]),
+                    "+v"(t[2]), "+v"(t[3]), "+v"(dt[0]), "+v"(dt[1]), "+v"(dt[2]), "+v"(dt[3]), "+v"(ap), "+v"(er));
+#endif
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = row0 + j * rpp;
+    if (lane && r < 8) dst[SG_X + 2 * r] = x[j], dst[SG_X + 2 * r + 1] = dx[j];
+    if (slotc && r < 8) dst[SG_C + 2 * r] = c[j], dst[SG_C + 2 * r + 1] = dc[j];
+  }
+  if (lane && row0 < 2) dst[SG_U + 2 * row0] = u, dst[SG_U + 2 * row0 + 1] = du;
+  if (first && tid < N) S.s[2 + tid] = ap;
+  if (first && tid >= 318) S.s[tid - 318] = er;
+  for (int rb = 0;;) {
+#pragma unroll
+    for (int j = 0; j < STG_TQ; j++) {
+      const int r = rb + row0 + j * rpp;
+      if (slotc && r < R) dst[SG_T + 2 * r] = t[j], dst[SG_T + 2 * r + 1] = dt[j];
+    }
+    if ((rb += STG_TQ * rpp) >= R) break;
+    load_t(rb);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(dt[0]), "+v"(dt[1]), "+v"(dt[2]), "+v"(dt[3]));
+#endif
+  }
+  if (first)
+    for (int kk = tid + 320; kk < N; kk += 320) S.s[2 + kk] = PL(W.SP, SP_apri, kk, N);  // (horizons beyond 320)
+}
+static_assert(STG_TQ == 4, "the register pins of d_step1_stage name 4 passes of T and dT");
 
 // ------------------------------------------------------------------------------------------ k_step1
 // Narrow launches: the whole step selection of ONE instance per workgroup (both line-search phases, the filter test
@@ -728,21 +923,34 @@ __global__ void __launch_bounds__(320) k_step1(const Consts* __restrict__ Kp, co
   const bool rprof = W.DBG != nullptr && blockIdx.x == 0 && tid == 0;
   long long rt0 = rprof ? clock64() : 0;
 #define STOCK(q) if (rprof) { const long long t1 = clock64(); W.DBG[q] += (double)(t1 - rt0); rt0 = t1; }
-  for (int idx = tid; idx < N * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, ELL>(K, W, idx % N, b, 1 + idx / N, 1 + idx / N);
+  // ... from the instance's operands staged in LDS, a window of slots at a time (StepStage; N = 40: one window, read again by
+  // the update).  Section 8 of the clocks is the staging and the line search together.
+  __shared__ double stg[STG_WORDS];
+  StepStage S = step_stage(K, W, stg);
+  for (;;) {
+    const int cnt = N - S.k0 < S.ks ? N - S.k0 : S.ks;
+    d_step1_stage(W, S, tid, b, cnt);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, ELL>(K, W, S.k0 + idx % cnt, b, 1 + idx / cnt, 1 + idx / cnt, S);
+    if (S.k0 + cnt >= N) break;
+    __syncthreads();  // (the window's readers are through before the next one is written)
+    S.k0 += cnt;
+  }
   STOCK(8);
   __syncthreads();
   STOCK(9);
   // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
   //  measures of all candidates exist already: one pass, same decisions)
   // ... on 8 lanes of wavefront 0; the other wavefronts fetch the operands of the update meanwhile (d_update_fetch: nothing of
-  // them is held across the pick by wavefront 0, whose batch of loads needs the registers)
+  // them is held across the pick by wavefront 0, whose batch of loads needs the registers); what the window holds is read from
+  // it after the barrier (d_update_store)
   UpdRegs upd;
   if (tid < 64) {
     if ((tid & 7) == 0) d_pick(K, W, b, tid >> 3, 1, false);
-  } else d_update_fetch(K, W, tid, b, upd);
+  } else d_update_fetch(K, W, S, tid, b, upd);
   __syncthreads();
   STOCK(10);
-  d_update_store(K, W, tid, b, upd);
+  d_update_store(K, W, S, tid, b, upd);
   STOCK(11);
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK
@@ -765,21 +973,34 @@ __global__ void __launch_bounds__(320) k_step1_pi(const Consts* __restrict__ Kp,
   const bool rprof = W.DBG != nullptr && blockIdx.x == 0 && tid == 0;
   long long rt0 = rprof ? clock64() : 0;
 #define STOCK(q) if (rprof) { const long long t1 = clock64(); W.DBG[q] += (double)(t1 - rt0); rt0 = t1; }
-  for (int idx = tid; idx < N * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, false, true>(K, W, idx % N, b, 1 + idx / N, 1 + idx / N);
+  // ... from the instance's operands staged in LDS, a window of slots at a time (StepStage; N = 40: one window, read again by
+  // the update).  Section 8 of the clocks is the staging and the line search together.
+  __shared__ double stg[STG_WORDS];
+  StepStage S = step_stage(K, W, stg);
+  for (;;) {
+    const int cnt = N - S.k0 < S.ks ? N - S.k0 : S.ks;
+    d_step1_stage(W, S, tid, b, cnt);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, false, true>(K, W, S.k0 + idx % cnt, b, 1 + idx / cnt, 1 + idx / cnt, S);
+    if (S.k0 + cnt >= N) break;
+    __syncthreads();  // (the window's readers are through before the next one is written)
+    S.k0 += cnt;
+  }
   STOCK(8);
   __syncthreads();
   STOCK(9);
   // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
   //  measures of all candidates exist already: one pass, same decisions)
   // ... on 8 lanes of wavefront 0; the other wavefronts fetch the operands of the update meanwhile (d_update_fetch: nothing of
-  // them is held across the pick by wavefront 0, whose batch of loads needs the registers)
+  // them is held across the pick by wavefront 0, whose batch of loads needs the registers); what the window holds is read from
+  // it after the barrier (d_update_store)
   UpdRegs upd;
   if (tid < 64) {
     if ((tid & 7) == 0) d_pick<true>(K, W, b, tid >> 3, 1, false);
-  } else d_update_fetch(K, W, tid, b, upd);
+  } else d_update_fetch(K, W, S, tid, b, upd);
   __syncthreads();
   STOCK(10);
-  d_update_store(K, W, tid, b, upd);
+  d_update_store(K, W, S, tid, b, upd);
   STOCK(11);
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK
@@ -801,21 +1022,34 @@ __global__ void __launch_bounds__(320) k_step1_ts(const Consts* __restrict__ Kp,
   const bool rprof = W.DBG != nullptr && blockIdx.x == 0 && tid == 0;
   long long rt0 = rprof ? clock64() : 0;
 #define STOCK(q) if (rprof) { const long long t1 = clock64(); W.DBG[q] += (double)(t1 - rt0); rt0 = t1; }
-  for (int idx = tid; idx < N * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, false, true, true>(K, W, idx % N, b, 1 + idx / N, 1 + idx / N);
+  // ... from the instance's operands staged in LDS, a window of slots at a time (StepStage; N = 40: one window, read again by
+  // the update).  Section 8 of the clocks is the staging and the line search together.
+  __shared__ double stg[STG_WORDS];
+  StepStage S = step_stage(K, W, stg);
+  for (;;) {
+    const int cnt = N - S.k0 < S.ks ? N - S.k0 : S.ks;
+    d_step1_stage(W, S, tid, b, cnt);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * K.o.n_linesearch; idx += 320) d_linesearch<BP, false, false, true, true>(K, W, S.k0 + idx % cnt, b, 1 + idx / cnt, 1 + idx / cnt, S);
+    if (S.k0 + cnt >= N) break;
+    __syncthreads();  // (the window's readers are through before the next one is written)
+    S.k0 += cnt;
+  }
   STOCK(8);
   __syncthreads();
   STOCK(9);
   // (phase 1 of the filter test starts with the test of the full step, i.e. it is phase 0 followed by phase 1 when the
   //  measures of all candidates exist already: one pass, same decisions)
   // ... on 8 lanes of wavefront 0; the other wavefronts fetch the operands of the update meanwhile (d_update_fetch: nothing of
-  // them is held across the pick by wavefront 0, whose batch of loads needs the registers)
+  // them is held across the pick by wavefront 0, whose batch of loads needs the registers); what the window holds is read from
+  // it after the barrier (d_update_store)
   UpdRegs upd;
   if (tid < 64) {
     if ((tid & 7) == 0) d_pick<true, true>(K, W, b, tid >> 3, 1, false);
-  } else d_update_fetch(K, W, tid, b, upd);
+  } else d_update_fetch(K, W, S, tid, b, upd);
   __syncthreads();
   STOCK(10);
-  d_update_store(K, W, tid, b, upd);
+  d_update_store(K, W, S, tid, b, upd);
   STOCK(11);
   if (rprof) W.DBG[12] += 1.0;
 #undef STOCK
